@@ -13,6 +13,12 @@ Workloads (--workload):
   A       config A: VLP-16 scan (~13k queries) vs the previous scan, inputs resident in HBM.
 --solver LS (default) or RANSAC_DRPM (the shipped config.json solver: RANSAC → DRPM).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (metric, value,
+unit, ms_per_step, ... and the configuration); `--dump-outputs DIR` also writes what the last timed
+step computed (dump_outputs).  Everything else below — the bit-equality check of the timed results,
+the pose exchange, the latency probe, the statistics / busy passes and the roofline, the CPU
+baseline with its oracle parity, config B's host hand-over leg — runs only with `--full`.
+
 Measurement: the timed region (barrier + synchronize on both sides, max over ranks) carries no
 instrumentation.  A separate probe afterwards registers `--latency-pairs` pairs ONE AT A TIME with
 HIP events around every projection launch (on the stream it runs on): single-pair latency
@@ -877,12 +883,87 @@ def host_leg(pairs, p, dev, local, args, world, fuse):
                                "FIFO content (single-frame kernels), bit for bit"}}
 
 
+DUMP_MAX_RESULTS = 4096   # dump_outputs: ~360 B per trace record x 20 iterations x 4096 results ≈ 30 MB
+
+
+def dump_outputs(dirpath, last) -> None:
+    """--dump-outputs: what the timed path handed its caller for the LAST timed step's
+    registrations — the tagged results (context, pose, iterations, status, per-iteration trace) of
+    every pair / frame launched in that step, ordered by context index — as DIR/<name>.npy, all
+    float64 (the counters are exact in it).  Traces shorter than the longest are NaN-padded.  Above
+    DUMP_MAX_RESULTS results a fixed seeded sample of the contexts is written (context.npy names
+    them).  The inputs are seeded, so two builds run with the same arguments write comparable files."""
+    d = pathlib.Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    last = sorted(last, key=lambda r: r[0])
+    if len(last) > DUMP_MAX_RESULTS:
+        keep = np.sort(np.random.default_rng(0).choice(len(last), DUMP_MAX_RESULTS, replace=False))
+        last = [last[i] for i in keep]
+    n = len(last)
+    T = max([len(r[4]) for r in last] + [0])
+    f8 = np.float64
+    delta, tpose = np.full((n, T, 4, 4), np.nan, f8), np.full((n, T, 4, 4), np.nan, f8)
+    reject = np.full((n, T, _abi.IMLS_NUM_REJ), np.nan, f8)
+    n_valid, n_kept = np.full((n, T), np.nan, f8), np.full((n, T), np.nan, f8)
+    for i, r in enumerate(last):
+        for j, t in enumerate(r[4]):
+            delta[i, j] = np.array(t.delta[:], f8).reshape(4, 4)
+            tpose[i, j] = np.array(t.pose[:], f8).reshape(4, 4)
+            reject[i, j] = t.reject[:]
+            n_valid[i, j], n_kept[i, j] = t.n_valid, t.n_kept
+    arrays = {
+        "context": np.array([r[0] for r in last], f8),
+        "pose": np.asarray([r[1] for r in last], f8).reshape(n, 4, 4),
+        "iterations": np.array([r[2] for r in last], f8),
+        "status": np.array([r[3] for r in last], f8),
+        "trace_delta": delta, "trace_pose": tpose, "trace_reject": reject,
+        "trace_n_valid": n_valid, "trace_n_kept": n_kept,
+    }
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    log(f"outputs of the last timed step: {n} result(s), {sum(a.nbytes for a in arrays.values()) / 1e6:.2f} MB in {d}")
+
+
+def describe(args, P: int, fuse: bool):
+    """(metric, workload description, unit) of the result line."""
+    if args.workload == "B":
+        metric = "IMLS-ICP scan-pairs/s (HDL-64 ~120k-pt scan vs 10-scan map, 20 ICP iterations)"
+        workload = f"config B: HDL-64 scan vs 10-scan local map; a step = {P} independent scan pairs" + (f" as {args.groups} launch sequences in flight" if fuse else " in flight, one stream each")
+        if args.host_inputs:
+            workload += ("; host hand-over: each pair's map is a device FIFO of its 10 scans, the newest scan and the "
+                         "source cross PCIe as 48-B PointXYZINormal records in every registration")
+        unit = "scan-pairs/s"
+    elif args.workload == "E":
+        metric = ("IMLS-ICP scan-pairs/s (config E: tensor-voting normals + IMLS on sparse VLP-16 planetary scans, "
+                  "20 ICP iterations)")
+        workload = f"config E: planetary VLP-16 scan vs the previous scan, tensor voting; a step = {P} independent pairs" + (" in one launch sequence" if fuse else " in flight, one stream each")
+        unit = "scan-pairs/s"
+    elif args.workload == "A":
+        metric = "IMLS-ICP scan-pairs/s (config A: VLP-16 scan vs 1-scan map, 20 ICP iterations)"
+        workload = f"config A: VLP-16 scan vs the previous scan; a step = {P} independent pairs" + (" in one launch sequence" if fuse else " in flight, one stream each")
+        unit = "scan-pairs/s"
+    else:
+        metric = ("IMLS-ICP frames/s (config C/D-like stream: producer-sampled <=2000-pt flat clouds of HDL-64 "
+                  "sweeps vs the device map FIFO, 20 ICP iterations" +
+                  (", host hand-over: PCIe of the new scan included)" if args.host_inputs else
+                   ", frames resident in HBM)"))
+        workload = f"config C/D-like: {P} independent sequences, one frame each per step" + (" in one launch sequence" if fuse else ", one stream each")
+        unit = "frames/s"
+    return metric, workload, unit
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the bit-equality "
+                         "check of the timed results, the pose exchange, the latency probe, the statistics and busy "
+                         "passes (roofline), the CPU baseline with its oracle parity, config B's host hand-over leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step's registrations as DIR/<name>.npy (float64)")
     ap.add_argument("--queries", type=int, default=0, help="config B: 0 = all source points; else FPS subsample")
     ap.add_argument("--inflight", type=int, default=0,
                     help="independent pairs / sequences per step (0 = workload default: B 4, A 256, stream 1024)")
@@ -900,11 +981,11 @@ def main():
                     help="B: inputs already resident in HBM" + (" (the default for B is the host hand-over: "
                          "--host-inputs)" if B_HOST_DEFAULT else " (already the default for B; the host "
                          "hand-over is --host-inputs, and the headline line carries it as host_handover)"))
-    ap.add_argument("--latency-pairs", type=int, default=50, help="single-pair latency / roofline probe size")
-    ap.add_argument("--busy-steps", type=int, default=5, help="steps of the HIP-event busy-time pass (0 = skip)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU-baseline leg")
-    ap.add_argument("--no-host-leg", action="store_true", help="config B: skip the host hand-over leg")
-    ap.add_argument("--no-verify", action="store_true", help="skip the bit-equality check of the timed results")
+    ap.add_argument("--latency-pairs", type=int, default=50, help="--full: single-pair latency / roofline probe size")
+    ap.add_argument("--busy-steps", type=int, default=5, help="--full: steps of the HIP-event busy-time pass (0 = skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU-baseline leg")
+    ap.add_argument("--no-host-leg", action="store_true", help="--full, config B: skip the host hand-over leg")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the bit-equality check of the timed results")
     ap.add_argument("--backend", choices=["auto", "nccl", "gloo"], default="auto")
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"))
     ap.add_argument("--workload", choices=["B", "stream", "A", "E"], default="B")
@@ -973,7 +1054,7 @@ def main():
     # the stream's frame of each result: the (map, source) frames loaded when its batch was prepared
     # (host-input pairs: the FIFO rotation of each result's load)
     frames_at_launch = {}
-    tag_loads = stream or (args.host_inputs and not stream)
+    tag_loads = args.full and (stream or args.host_inputs)   # read by the verification below only
     if tag_loads and stream:
         orig_prep = runner._prep
 
@@ -1010,8 +1091,57 @@ def main():
             f"rest {(elapsed - runner.pipe.t_wait - runner.pipe.t_launch - runner.pipe.t_prep - runner.pipe.t_tag) / args.steps * 1e3:.2f} ms")
     n_pairs = args.steps * P
     value = world * n_pairs / elapsed
+    ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res[-P:])   # the registrations launched in the last timed step
+    stats0 = probe_ctx.index_stats()
+    metric, workload, unit = describe(args, P, fuse)
+    per = np.array(per_step) * 1e3
+    solver_txt = "LS (trimmed, t=0.02)" if args.solver == "LS" else "RANSAC -> DRPM (shipped config.json solver)"
+    out = {
+        "metric": metric,
+        "value": value,
+        "unit": unit,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "ms_per_step_median": float(np.median(per)),
+        "ms_per_step_p90": float(np.percentile(per, 90)),
+        "ms_per_pair": elapsed / n_pairs * 1e3,
+        "pairs_in_flight": P,
+        "ms_per_iteration": elapsed / n_pairs * 1e3 / args.iters,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (seeded HDL-64 / VLP-16 ray-cast urban scene, planetary-lidar-odometry_amd/synth.py)",
+        "full": args.full,
+        "config": {
+            "workload": workload,
+            "queries": int(stats0["queries"]) if not stream else queries,
+            "map_points": int(stats0["points"]) if not stream else map_points,
+            "icp_iterations": args.iters,
+            "solver": solver_txt,
+            "search_number": p.search_number,
+            "inputs": "host memory (PCIe inside the timed region)" if args.host_inputs else "resident in HBM",
+            "fused_launch": fuse,
+            "launch_groups": args.groups if fuse else P,
+            "parallelism": (f"independent pairs per GPU over {world} GPU(s), {dist.get_backend()} "
+                            f"({'RCCL' if dist.get_backend() == 'nccl' else 'CPU'}) pose all-gather"
+                            if _grouped() else "1 GPU, no process group"),
+        },
+    }
+    if not args.full:
+        # a plain run ends here: the headline line alone
+        runner.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if _grouped():
+            dist.destroy_process_group()
+        return
 
-    # ---- outside the timed region -------------------------------------------------------------
+    # ---- outside the timed region (--full) ----------------------------------------------------
     # (1) every timed result bit-equal to its pair registered alone (single-frame kernels)
     verify = None
     worst = 0
@@ -1121,7 +1251,6 @@ def main():
     # first and hands this run the fresh file; the driver's plain run reads the round's committed one
     traffic = traffic_meta = None
     tj = pathlib.Path(args.traffic_json)
-    stats0 = probe_ctx.index_stats()
     if tj.exists() and args.workload == "B":
         try:
             tdat = json.loads(tj.read_text())
@@ -1160,7 +1289,6 @@ def main():
 
     # (5) roofline of the projection step (HBM-bound by the survey's accounting)
     roof = None
-    ms_step = elapsed / args.steps * 1e3
     agg = bytes_per_step / (ms_step / 1e3) / 1e9
     roof = {
         "bound": "hbm",
@@ -1200,66 +1328,10 @@ def main():
             "achieved": b_launch / (dom_ms / 1e3) / 1e9 if dom_ms > 0 else 0.0,
             "frac": b_launch / (dom_ms / 1e3) / 1e9 / HBM_PEAK_GBS if dom_ms > 0 else 0.0}
 
-    solver_txt = "LS (trimmed, t=0.02)" if args.solver == "LS" else "RANSAC -> DRPM (shipped config.json solver)"
-    if args.workload == "B":
-        metric = "IMLS-ICP scan-pairs/s (HDL-64 ~120k-pt scan vs 10-scan map, 20 ICP iterations)"
-        workload = f"config B: HDL-64 scan vs 10-scan local map; a step = {P} independent scan pairs" + (f" as {args.groups} launch sequences in flight" if fuse else " in flight, one stream each")
-        if args.host_inputs:
-            workload += ("; host hand-over: each pair's map is a device FIFO of its 10 scans, the newest scan and the "
-                         "source cross PCIe as 48-B PointXYZINormal records in every registration")
-        unit = "scan-pairs/s"
-    elif args.workload == "E":
-        metric = ("IMLS-ICP scan-pairs/s (config E: tensor-voting normals + IMLS on sparse VLP-16 planetary scans, "
-                  "20 ICP iterations)")
-        workload = f"config E: planetary VLP-16 scan vs the previous scan, tensor voting; a step = {P} independent pairs" + (" in one launch sequence" if fuse else " in flight, one stream each")
-        unit = "scan-pairs/s"
-    elif args.workload == "A":
-        metric = "IMLS-ICP scan-pairs/s (config A: VLP-16 scan vs 1-scan map, 20 ICP iterations)"
-        workload = f"config A: VLP-16 scan vs the previous scan; a step = {P} independent pairs" + (" in one launch sequence" if fuse else " in flight, one stream each")
-        unit = "scan-pairs/s"
-    else:
-        metric = ("IMLS-ICP frames/s (config C/D-like stream: producer-sampled <=2000-pt flat clouds of HDL-64 "
-                  "sweeps vs the device map FIFO, 20 ICP iterations" +
-                  (", host hand-over: PCIe of the new scan included)" if args.host_inputs else
-                   ", frames resident in HBM)"))
-        workload = f"config C/D-like: {P} independent sequences, one frame each per step" + (" in one launch sequence" if fuse else ", one stream each")
-        unit = "frames/s"
-    per = np.array(per_step) * 1e3
     first_traj = next(iter(trajs.values()), None)
-    out = {
-        "metric": metric,
-        "value": value,
-        "unit": unit,
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "ms_per_step_median": float(np.median(per)),
-        "ms_per_step_p90": float(np.percentile(per, 90)),
-        "ms_per_pair": elapsed / n_pairs * 1e3,
-        "pairs_in_flight": P,
-        "ms_per_iteration": elapsed / n_pairs * 1e3 / args.iters,
+    out.update({
         "single_pair": probe,
         "single_frame": single_frame,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded HDL-64 / VLP-16 ray-cast urban scene, planetary-lidar-odometry_amd/synth.py)",
-        "config": {
-            "workload": workload,
-            "queries": int(stats0["queries"]) if not stream else queries,
-            "map_points": int(stats0["points"]) if not stream else map_points,
-            "icp_iterations": args.iters,
-            "solver": solver_txt,
-            "search_number": p.search_number,
-            "inputs": "host memory (PCIe inside the timed region)" if args.host_inputs else "resident in HBM",
-            "fused_launch": fuse,
-            "launch_groups": args.groups if fuse else P,
-            "parallelism": (f"independent pairs per GPU over {world} GPU(s), {dist.get_backend()} "
-                            f"({'RCCL' if dist.get_backend() == 'nccl' else 'CPU'}) pose all-gather"
-                            if _grouped() else "1 GPU, no process group"),
-        },
         "verify": verify,
         "parity": parity,
         "roofline": roof,
@@ -1269,7 +1341,7 @@ def main():
         "trajectory_end_seq0": first_traj[1][-1][:3, 3].tolist() if first_traj is not None and len(first_traj[1]) else None,
         "cpu_baseline": cpu,
         "host_handover": None,
-    }
+    })
     runner.close()
     if want_leg:
         out["host_handover"] = run_leg()

@@ -15,7 +15,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for v in product ${VARS:-}; do
     lib=""; [ $v = product ] || lib=$C/var_$v/libimls_gpu.so
     f=$O/${v}_$r
-    env ${lib:+IMLS_LIB_PATH=$lib} timeout -k 10 300 python3 bench.py --no-cpu --steps ${STEPS:-8} --latency-pairs 10 ${BENCH_ARGS:-} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+    env ${lib:+IMLS_LIB_PATH=$lib} timeout -k 10 300 python3 bench.py --full --no-cpu --steps ${STEPS:-8} --latency-pairs 10 ${BENCH_ARGS:-} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
     show $f.json "$v $r"
   done
 done

@@ -22,15 +22,15 @@ show() { python3 -c "
 import json;d=json.loads(open('$1').read().strip().splitlines()[-1]);r=d['roofline'];s=r.get('serialised_single_pair',{}).get('kernel_avg_ms',{})
 print('$2', round(d['value'],1), 'busy_proj', round(r.get('busy_projection_ms_per_step',0),2), 'knn', round(s.get('k_knn_wave',0)*1e3,1), 'finish', round(s.get('k_finish',0)*1e3,1), 'single', round(d['single_pair']['median_ms'],2))"; }
 for r in $(seq 1 ${ROUNDS:-2}); do
-  timeout -k 10 300 python3 bench.py --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $O/base_$r.json 2> $O/base_$r.err || { tail -5 $O/base_$r.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $O/base_$r.json 2> $O/base_$r.err || { tail -5 $O/base_$r.err; exit 1; }
   show $O/base_$r.json "base $r"
-  IMLS_LIB_PATH=$V timeout -k 10 300 python3 bench.py --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $O/var_$r.json 2> $O/var_$r.err || { tail -5 $O/var_$r.err; exit 1; }
+  IMLS_LIB_PATH=$V timeout -k 10 300 python3 bench.py --full --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $O/var_$r.json 2> $O/var_$r.err || { tail -5 $O/var_$r.err; exit 1; }
   show $O/var_$r.json "variant $r"
 done
 kn=0
 for k in ${KNOBS:-}; do   # product library with NAME=VALUE knobs (several joined by '+')
   f=$O/knob_$(echo "$k" | tr '/' '_')_$((++kn))
-  timeout -k 10 300 env ${k//+/ } python3 bench.py --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+  timeout -k 10 300 env ${k//+/ } python3 bench.py --full --no-cpu --steps 8 --latency-pairs 10 ${BENCH_ARGS:-} > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
   show $f.json "$k"
 done
 if [ "${SKIP_DUMP:-0}" != 1 ]; then

@@ -21,7 +21,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for k in ${KNOBS:-base}; do
     f=$O/r${r}_$((++kn))
     envs=${k//+/ }; [ "$k" = base ] && envs="IMLS_NOTHING=0"
-    timeout -k 10 300 env $envs python3 bench.py --no-cpu --steps ${STEPS:-8} --latency-pairs ${LAT:-10} ${BENCH_ARGS:-} > $f.json 2> $f.err \
+    timeout -k 10 300 env $envs python3 bench.py --full --no-cpu --steps ${STEPS:-8} --latency-pairs ${LAT:-10} ${BENCH_ARGS:-} > $f.json 2> $f.err \
       || { echo "bench $k failed"; tail -5 $f.err; exit 1; }
     show $f.json "$k r$r"
   done

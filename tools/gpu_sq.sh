@@ -7,7 +7,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 timeout -k 10 300 python3 -u -m pytest tests/test_gpu_frames.py -m gpu -x -q --timeout 120 --timeout-method thread > $O/tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -2 $O/tests.log; [ $rc -eq 0 ] || exit $rc
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu --inflight 1 --no-fuse --latency-pairs 3"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu --inflight 1 --no-fuse --latency-pairs 3"
 run() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 --kernel-trace --kernel-include-regex 'k_knn_wave|k_finish' --output-format csv \

@@ -7,7 +7,7 @@ set -u
 O=gpurun_out/${OUT:-sq4}
 mkdir -p $O
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu --latency-pairs 2 --busy-steps 0 --no-verify"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu --latency-pairs 2 --busy-steps 0 --no-verify"
 run() {  # name, env, counters...
   local name=$1 envs=$2; shift 2
   timeout -s KILL 240 env $envs rocprofv3 --kernel-trace --kernel-include-regex 'k_knn_wave_b|k_finish_b' --output-format csv \

@@ -6,7 +6,7 @@ set -u
 O=gpurun_out/${OUT:-sqi}
 mkdir -p $O
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu --no-verify --inflight 1 --no-fuse --latency-pairs 3 --busy-steps 0"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-verify --inflight 1 --no-fuse --latency-pairs 3 --busy-steps 0"
 for v in ${VARIANTS:-base}; do
   envs=""; [ "$v" = base ] || envs="${v//+/ }"
   for e in $envs; do export "$e"; done

@@ -15,18 +15,18 @@ step() {
 if [ "${PART:-1}" = 1 ]; then
 [ "${SKIP_TESTS:-0}" = 1 ] || step gpu_tests 700 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-step bench_B 600 python3 bench.py
-step bench_stream 300 python3 bench.py --workload stream
+step bench_B 600 python3 bench.py --full
+step bench_stream 300 python3 bench.py --full --workload stream
 fi
 if [ "${PART:-1}" = 2 ]; then
-step bench_stream_host 300 python3 bench.py --workload stream --no-cpu --host-inputs
-step bench_stream_ransac 400 python3 bench.py --workload stream --no-cpu --solver RANSAC_DRPM
-step bench_A 400 python3 bench.py --workload A
-step bench_E 500 python3 bench.py --workload E
-step bench_B_q2000 400 python3 bench.py --queries 2000
-step bench_A_ransac 400 python3 bench.py --workload A --solver RANSAC_DRPM
-step bench_B_host 400 python3 bench.py --host-inputs --no-cpu
+step bench_stream_host 300 python3 bench.py --full --workload stream --no-cpu --host-inputs
+step bench_stream_ransac 400 python3 bench.py --full --workload stream --no-cpu --solver RANSAC_DRPM
+step bench_A 400 python3 bench.py --full --workload A
+step bench_E 500 python3 bench.py --full --workload E
+step bench_B_q2000 400 python3 bench.py --full --queries 2000
+step bench_A_ransac 400 python3 bench.py --full --workload A --solver RANSAC_DRPM
+step bench_B_host 400 python3 bench.py --full --host-inputs --no-cpu
 step dist1 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu
+    --master-port 29517 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu
 fi
 echo done

@@ -3,7 +3,7 @@
 set -u
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu"
 timeout -k 10 120 rocprofv3 -L > gpurun_out/pmc/counters_list.txt 2>&1 || true
 i=0
 for set in "${PMC_SETS[@]:-}"; do :; done

@@ -12,7 +12,7 @@ for r in 1 2; do
   for cfg in "4 4" "4 2" "8 4" "6 6" "3 3"; do
     set -- $cfg
     f=$O/B_p$1_g$2_$r
-    timeout -k 10 300 python3 bench.py --no-cpu --no-host-leg --steps 8 --latency-pairs 3 --inflight $1 --groups $2 > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --no-cpu --no-host-leg --steps 8 --latency-pairs 3 --inflight $1 --groups $2 > $f.json 2> $f.err || { tail -5 $f.err; exit 1; }
     show $f.json "inflight $1 groups $2 round $r"
   done
 done

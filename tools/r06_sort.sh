@@ -13,7 +13,7 @@ rc=$?; echo "tests rc=$rc"; tail -3 $O/tests.log; [ $rc -eq 0 ] || exit $rc
 for r in 1 2; do
   for v in product cubsort; do
     lib=""; [ $v = product ] || lib=planetary-lidar-odometry_amd/csrc/var_$v/libimls_gpu.so
-    env ${lib:+IMLS_LIB_PATH=$lib} timeout -k 10 300 python3 bench.py --no-cpu --steps 8 --latency-pairs 5 > $O/${v}_$r.json 2> $O/${v}_$r.err || { tail -5 $O/${v}_$r.err; exit 1; }
+    env ${lib:+IMLS_LIB_PATH=$lib} timeout -k 10 300 python3 bench.py --full --no-cpu --steps 8 --latency-pairs 5 > $O/${v}_$r.json 2> $O/${v}_$r.err || { tail -5 $O/${v}_$r.err; exit 1; }
     python3 -c "
 import json;d=json.loads(open('$O/${v}_$r.json').read().strip().splitlines()[-1]);h=d['host_handover']
 print('$v $r', round(d['value'],1), 'host', round(h['value'],1), 'idx_ms', round(h['index_ms_per_registration'],4), 'single', round(d['single_pair']['median_ms'],3), 'index', round(d['single_pair']['kernel_avg_ms']['index'],4))"

@@ -12,6 +12,6 @@ step() {  # name, timeout, command...
 }
 step gpu_tests 800 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-step bench_B 600 python3 bench.py
+step bench_B 600 python3 bench.py --full
 OUT=${OUT:-r06_start}/sq4 bash tools/gpu_sq4.sh > $O/sq4.log 2>&1; echo "sq4 rc=$?"
 echo done
