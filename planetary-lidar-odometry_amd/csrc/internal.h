@@ -78,16 +78,11 @@ struct KParams {
     int tv_k;                 // use_tensor_voting.k (≤ kTvMaxK)
     double tv_sigma, tv_thr;  // use_tensor_voting.sigma, .distance_threshold
     float tv_skin;            // TV ball lists reused while the query moved ≤ skin (m); 0 = every iteration walks the tree
-    int bfs;                  // this launch's packet walks start breadth-first (the first IMLS_BFS_ITERS iterations)
 };
 // the parameters of ICP iteration `it`'s projection launch (packet size of the traversal)
-#ifndef IMLS_BFS_ITERS
-#define IMLS_BFS_ITERS 0   // breadth-first top levels: measured slower (profiles/r06_bfs_rejected/), off
-#endif
 inline KParams kp_at(const KParams& k, int it) {
     KParams r = k;
     r.packet = it >= 0 && it < k.pk_iters ? k.pk_small : 64;
-    r.bfs = it >= 0 && it < IMLS_BFS_ITERS;
     return r;
 }
 constexpr int kTvMaxK = 64;    // tensor-voting kNN size handled on device
@@ -387,16 +382,8 @@ constexpr int kMaxKL = 46;       // list entries per query at most (the lone-fra
 __host__ __device__ inline float4* xref_of(int* lists, int N) {
     return reinterpret_cast<float4*>(reinterpret_cast<char*>(lists) + ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256);
 }
-// then the compacted traversal lists of the packet kernel's later ICP iterations (round 6: per
-// traversal block, the slots whose list could not be reused, unsigned cmp[N]) and their counts (one
-// word per block, cmp_count[N / 64 + 1])
-__host__ __device__ inline unsigned* cmp_of(int* lists, int N) {
-    return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xref_of(lists, N)) + ((size_t)N * 20 + 255) / 256 * 256);
-}
-__host__ __device__ inline unsigned* cmp_count_of(int* lists, int N) { return cmp_of(lists, N) + ((size_t)N + 63) / 64 * 64; }
 inline size_t prevnn_bytes(int N) {
-    return ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256 + ((size_t)N * 20 + 255) / 256 * 256 + ((size_t)N + 63) / 64 * 256 +
-           ((size_t)N / 64 + 2) * 4 + 512;
+    return ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256 + ((size_t)N * 20 + 255) / 256 * 256 + 512;
 }
 constexpr int kStatSkipped = 6;   // nbr_stats slot: lanes whose list was reused without traversal
 int project_blocks(int N);

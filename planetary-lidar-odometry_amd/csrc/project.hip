@@ -35,6 +35,19 @@
 #include "internal.h"
 #include "geom.h"
 
+// v_writelane_b32: `old` with lane `sel`'s value replaced by the wave-uniform `v` (every lane
+// takes part, whatever exec says); v and sel must be wave-uniform.  The documented builtin where
+// the compiler has it; the clang of ROCm 7.2 has none, and there the LLVM intrinsic
+// llvm.amdgcn.writelane (AMDGPUUsage) is declared under its own name — a declaration, not inline
+// assembly: the kernel holds no asm beyond empty pins.
+#if defined(__has_builtin) && __has_builtin(__builtin_amdgcn_writelane)
+__device__ __forceinline__ int imls_amdgcn_writelane(int v, int sel, int old) {
+    return __builtin_amdgcn_writelane(v, sel, old);
+}
+#else
+__device__ int imls_amdgcn_writelane(int v, int sel, int old) __asm("llvm.amdgcn.writelane");
+#endif
+
 namespace imlsgpu {
 namespace {
 
@@ -53,12 +66,6 @@ constexpr int kFallbackBlocksBatched = 4;   // physical blocks per frame of a la
 // queries per k_finish block = per pass-1 slab (the quad exact stage: 64; the one-lane form: 256)
 constexpr int kFinishPerBlock = IMLS_FINISH_QUAD ? kWaveBlock / 4 : kWaveBlock;
 static_assert(kFinishPerBlock == kPass1Block && kFallbackBlocks == kPass1Fallback, "pass-1 slab layout (solve.hip)");
-// the later ICP iterations' packet traversal in two launches (reuse decision + compacted walk, round 6):
-// measured slower (a walk's cost is its node visits, which compaction only concentrates into fewer,
-// longer walks — profiles/r06_compact_rejected/), off; kept for same-box A/B builds
-#ifndef IMLS_COMPACT
-#define IMLS_COMPACT 0
-#endif
 constexpr int kWideMax = 8;         // packet traversal: children tested per step (2^wide, wide ≤ 3)
 constexpr int kWaveStack = 64;       // its stack: ≤ 7 entries per step × ⌈23/3⌉ steps
 constexpr int kFStack = 256;        // frontier traversal's stack per wave (see knn_qwave_body)
@@ -524,22 +531,11 @@ __device__ __forceinline__ float need_key_ids(const float (&lk)[KL], float r2, i
 #define IMLS_KNN_WAVES 5
 #endif
 #define IMLS_KNN_ATTR __attribute__((amdgpu_waves_per_eu(KL <= 26 ? IMLS_KNN_WAVES : 2)))
-// MODE (round 6, the later ICP iterations of the packet traversal, use_prev):
-//   0  one pass — every lane decides reuse and the packets walk for the lanes that cannot reuse;
-//   1  the reuse decision only (Verlet skip, prefill certificate): a reused list is settled here,
-//      the block's other slots are compacted, in slot (Morton) order, into the block's own region
-//      of cmp, with their count in cmp_count[block];
-//   2  the walk over a block's compacted slots, 64 to a packet: fewer packets walk, each full of
-//      queries that really re-traverse, from the block's 4·64 Morton-consecutive slots (instead of
-//      every packet walking for the few of its lanes that do).  The lane redoes MODE 1's decision
-//      (same inputs, same outcome), its prefill included.
-//   3  the first ICP iterations' walk with a breadth-first top (k_knn_wave_bfs[b], IMLS_BFS_ITERS):
-//      the upper levels expanded against the packet's box, the frontier handed to the depth-first
-//      stack.  Measured slower (profiles/r06_bfs_rejected/): off by default, kept for A/B builds.
-// (A first version compacted through one atomic counter per frame: packets of runs from anywhere in
-// the frame walked 2-6× longer — profiles/r06_compact_rejected/.  Modes 1 and 2 are off as well:
-// IMLS_COMPACT.)
-template <int KL, int MODE = 0>
+// One pass: every lane decides reuse, and the packet walks for the lanes that cannot reuse.  (Round 6
+// tried a compacted second launch for the later iterations and a breadth-first top for the first
+// ones; both measured slower — profiles/r06_compact_rejected/, profiles/r06_bfs_rejected/ — and
+// were removed in round 7.)
+template <int KL>
 __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restrict__ spt,
                                                          const unsigned* __restrict__ qperm, int N,
                                                          const double* __restrict__ pose,
@@ -548,8 +544,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                                                          int* __restrict__ lists, float* __restrict__ wlist,
                                                          float4* __restrict__ xref, float* __restrict__ nref,
                                                          int use_prev, unsigned long long* __restrict__ nbr_stats,
-                                                         int bx, unsigned* __restrict__ cmp = nullptr,
-                                                         unsigned* __restrict__ cmp_count = nullptr) {
+                                                         int bx) {
     if (done && ld_const(done)) return;
     __shared__ int snode[kWaveBlock / 64][kWaveStack];
     __shared__ float4 sboxa[kWaveBlock / 64][kWaveStack];   // stacked node boxes: lo.xyz, hi.x
@@ -564,17 +559,8 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
     // most lanes seed: a smaller packet's union of neighbourhoods is smaller, and the launch lasts
     // as long as its slowest wave); lanes past the packet idle
     const int qp = kp.packet;
-    const int pslot = (bx * (kWaveBlock / 64) + wv) * qp + lane;
-    int slot = pslot;
-    bool active = lane < qp && slot < N;
-    if constexpr (MODE == 2) {
-        // packet = the block's compacted entries [wv·qp, wv·qp + qp); the count is the prep launch's
-        // (no block barrier in this mode: use_prev — a wave past it leaves at once)
-        const int cnt = ld_const((const int*)cmp_count + bx);
-        if (wv * qp >= cnt) return;
-        active = lane < qp && wv * qp + lane < cnt;
-        slot = active ? (int)cmp[(size_t)bx * (kWaveBlock / 64) * qp + wv * qp + lane] : 0;
-    }
+    const int slot = (bx * (kWaveBlock / 64) + wv) * qp + lane;
+    const bool active = lane < qp && slot < N;
     float xf[3] = {0.f, 0.f, 0.f};
     // the stored list's bound and reference (slot-indexed) load beside the query's point: one round
     // trip after the query index, not one more after the transform
@@ -614,7 +600,10 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
     };
     const float r2s = (float)(kp.r2 * kSearchR2) * kBoxSlack + 1e-30f;   // the search bound (radius (1 + skin)·r)
     float bnd = active ? r2s : -1.0f;
-    const int P = t.P, B = t.B, M = t.M;
+    // (pinned: scalars of their own — as members of the view's 8-dword kernel-argument tuple, every
+    // use inside the walk loop reloaded the whole spilled tuple, 8 v_readlane each)
+    int P = t.P, B = t.B, M = t.M;
+    asm volatile("" : "+s"(P), "+s"(B), "+s"(M));
 #ifdef IMLS_DEBUG_WAVE_TRACE
     const long long dbg_t0 = wall_clock64();
 #endif
@@ -699,32 +688,12 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             if (nk < kInfF && nk * (1.0f + 1e-5f) < wlow) { skip = true; wskip = wlow; }
         }
     }
-    if constexpr (MODE == 1) {
-        // settle the reused lists; compact the rest for the MODE 2 walk
-        if (active && skip) wlist[slot] = wskip;
-        const unsigned long long sk = __ballot(skip);
-        if (nbr_stats && lane == 0 && sk) atomicAdd(&nbr_stats[kStatSkipped], (unsigned long long)__popcll(sk));
-        const bool need = active && !skip;
-        const unsigned long long nm = __ballot(need);
-        __shared__ int wneed[kWaveBlock / 64];
-        if (lane == 0) wneed[wv] = __popcll(nm);
-        __syncthreads();              // every wave of the block reaches here (MODE 1 leaves below)
-        int off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < kWaveBlock / 64; ++w) {
-            off += w < wv ? wneed[w] : 0;
-            tot += wneed[w];
-        }
-        if (need) cmp[(size_t)bx * (kWaveBlock / 64) * qp + off + __popcll(nm & ((1ull << lane) - 1ull))] = (unsigned)slot;
-        if (tid == 0) cmp_count[bx] = (unsigned)tot;
-        return;
-    }
-    // leaf scan shared by the seed pass and the traversal: the lanes in `want` test every point of
+    // leaf scan of the traversal (its one call site): the lanes in `want` test every point of
     // leaf `leaf` against their bound; `listed`: the leaf may hold points already in a lane's
     // list (prefilled or seeded), which must not be inserted twice
 #ifdef IMLS_DEBUG_WAVE_TRACE
     unsigned dbg_ev = 0, dbg_ins = 0;
-    unsigned dbg_sparse = 0, dbg_bcast = 0, dbg_sparse_lanes = 0, dbg_sparse_ins = 0;
+    unsigned dbg_sparse = 0, dbg_bcast = 0, dbg_sparse_lanes = 0, dbg_listed_lv = 0;   // … sparse visits where a wanting lane has a listed point in the leaf
     unsigned dbg_seed_steps = 0, dbg_seed_pts = 0;   // seed points where any lane inserted / seed points scanned
 #endif
     // mine: lane k's point k of the leaf (loaded by the caller; zero past the leaf's count)
@@ -742,6 +711,11 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             }
         };
         const bool sparse = __popcll(want) <= kSparseLanes;
+        // the two scans are two ifs, the second's flag opaque (an empty pin), not an if/else: the
+        // structuriser's if/else gives the keys written in its first arm a register set of their own
+        // (see the walk loop's header)
+        int bcast = __builtin_amdgcn_readfirstlane(!sparse);
+        asm volatile("" : "+s"(bcast));
 #ifdef IMLS_DEBUG_WAVE_TRACE
         if (sparse) { ++dbg_sparse; dbg_sparse_lanes += __popcll(want); } else { ++dbg_bcast; }
 #endif
@@ -766,9 +740,18 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             if (listed) {
 #pragma unroll
                 for (int k = 0; k < KL; ++k) nin += (unsigned)(pos_(k) - base) < (unsigned)cnt ? 1 : 0;
+#ifdef IMLS_DEBUG_WAVE_TRACE
+                dbg_listed_lv += (__ballot(nin > 0) & want) ? 1 : 0;
+#endif
             }
             const float cb = fmin_nn(r2s, IK::hi(lk[KL - 1]));
-            unsigned long long cm = 0ull;
+            // lane q's candidate mask is written into lane q by v_writelane (two per trip: the mask is
+            // wave-uniform, in SGPRs) instead of a compare and two selects over all lanes; the
+            // in-leaf mask is one scalar AND on the compare's own mask (no trip through a VGPR)
+            int cm_lo = 0, cm_hi = 0;
+            // (cnt ≥ 1 for every leaf the walk admits — a padded leaf past M has an inverted box — as the
+            // broadcast scan's lp[cnt − 1] assumes too; clamped all the same: no undefined shift)
+            const unsigned long long inleaf = cnt >= 64 ? ~0ull : (1ull << max(cnt, 0)) - 1ull;
             unsigned long long m = want;
             while (m) {
                 const int q = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
@@ -779,7 +762,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 const float qb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cb), q));
                 const float ex = mine.x - qx, ey = mine.y - qy, ez = mine.z - qz;
                 const float d32 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-                unsigned long long pm = __ballot(lane < cnt && d32 <= qb);
+                unsigned long long pm = __ballot(d32 <= qb) & inleaf;
                 if (!have_inl) {
                     const int nq = __builtin_amdgcn_readlane(nin, q);
                     if (__popcll(pm) > nq) {
@@ -795,8 +778,10 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                         (unsigned)__builtin_amdgcn_readlane((int)(unsigned)inl, q);
                     pm &= ~inq;
                 }
-                if (lane == q) cm = pm;
+                cm_lo = imls_amdgcn_writelane((int)(unsigned)pm, q, cm_lo);
+                cm_hi = imls_amdgcn_writelane((int)(unsigned)(pm >> 32), q, cm_hi);
             }
+            unsigned long long cm = ((unsigned long long)(unsigned)cm_hi << 32) | (unsigned)cm_lo;
             while (__ballot(cm != 0ull)) {
                 // every lane takes part in the permutes (lanes without a candidate read lane 0)
                 const int jj = cm ? (int)__builtin_ctzll(cm) : 0;
@@ -817,7 +802,8 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 ++dbg_ev;
 #endif
             }
-        } else {
+        }
+        if (bcast) {
             if (listed) listed_mask();
             const bool wants = (want >> lane) & 1ull;
 #if IMLS_BCAST_SCALAR
@@ -969,105 +955,21 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
     unsigned long long em = __ballot(active && !skip);   // lanes whose bound admits the current node's box
     const unsigned long long skipped = __ballot(skip);
     if (nbr_stats && lane == 0 && skipped) atomicAdd(&nbr_stats[kStatSkipped], (unsigned long long)__popcll(skipped));
-    if constexpr (MODE == 3) {
-        // Breadth-first top of the walk (round 6, the first ICP iterations, whose waves walk ~55 dependent
-        // node / leaf steps): the upper levels are expanded a whole level-step at a time — one lane per
-        // frontier node, its 2^sw children tested against the packet's box (the union of the lanes'
-        // search balls, a superset of every lane's own test) — while the frontier plus the depth-first
-        // pushes still to come below it fit the wave's stack; the frontier then becomes that stack
-        // (Morton order on top) and the depth-first walk continues from it, every entry re-checked
-        // against the lanes' shrinking bounds at its pop.  Exact either way: nothing a lane's ball
-        // reaches is dropped (the box is inflated past fp32 rounding), and k_finish certifies each list.
-        if (em) {
-            const bool walk = active && !skip;
-            const float rr = walk ? sqrtf(bnd * kBoxSlack) * (1.0f + 1e-5f) + 1e-5f : 0.f;
-            float plo[3], phi[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                plo[a] = walk ? xf[a] - rr : kInfF;
-                phi[a] = walk ? xf[a] + rr : -kInfF;
-            }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    plo[a] = fminf(plo[a], __shfl_xor(plo[a], o, 64));
-                    phi[a] = fmaxf(phi[a], __shfl_xor(phi[a], o, 64));
-                }
-            int fc = 1, lev = 0;
-            if (lane == 0) snode[wv][0] = 1;
-            while (lev < t.levels) {
-                const int sw = min(kWide, t.levels - lev), nk = 1 << sw;
-                const int below = t.levels - lev - sw;
-                const int reserve = (kWideMax - 1) * ((below + kWide - 1) / kWide);
-                const int n = lane < fc ? snode[wv][lane] : 0;
-                const float4* rec = t.nodes + 3 * ((size_t)(n > 0 ? n : 1) << (sw - 1));
-                auto child_box = [&](int k, float (&lo)[3], float (&hi)[3]) {
-                    const float4 ra = rec[3 * (k >> 1)], rb = rec[3 * (k >> 1) + 1], rc = rec[3 * (k >> 1) + 2];
-                    if (k & 1) { lo[0] = rb.z; lo[1] = rb.w; lo[2] = rc.x; hi[0] = rc.y; hi[1] = rc.z; hi[2] = rc.w; }
-                    else { lo[0] = ra.x; lo[1] = ra.y; lo[2] = ra.z; hi[0] = ra.w; hi[1] = rb.x; hi[2] = rb.y; }
-                };
-                unsigned cm = 0u;
-                if (lane < fc) {
-#pragma unroll
-                    for (int k = 0; k < kWideMax; ++k) {
-                        if (k >= nk) break;
-                        float lo[3], hi[3];
-                        child_box(k, lo, hi);
-                        const bool ov = lo[0] <= phi[0] && hi[0] >= plo[0] && lo[1] <= phi[1] && hi[1] >= plo[1] &&
-                                        lo[2] <= phi[2] && hi[2] >= plo[2];
-                        cm |= ov ? (1u << k) : 0u;
-                    }
-                }
-                // exclusive prefix of the lanes' child counts (the next frontier keeps Morton order)
-                const int cnt = __popc(cm);
-                int inc = cnt;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(inc, o, 64);
-                    if (lane >= o) inc += v;
-                }
-                const int total = __shfl(inc, 63, 64);
-                if (total == 0 || total + reserve > kWaveStack) break;
-                int off = inc - cnt;
-                if (cm) {
-#pragma unroll
-                    for (int k = 0; k < kWideMax; ++k) {
-                        if (!((cm >> k) & 1u)) continue;
-                        float lo[3], hi[3];
-                        child_box(k, lo, hi);
-                        snode[wv][off] = (n << sw) + k;
-                        sboxa[wv][off] = make_float4(lo[0], lo[1], lo[2], hi[0]);
-                        sboxb[wv][off] = make_float2(hi[1], hi[2]);
-                        ++off;
-                    }
-                }
-                fc = total;
-                lev += sw;
-                ++n_inner;
-            }
-            if (lev > 0) {
-                // the frontier becomes the depth-first stack, its Morton-first entry on top
-                int en = 0;
-                float4 ea = make_float4(0.f, 0.f, 0.f, 0.f);
-                float2 eb = make_float2(0.f, 0.f);
-                if (lane < fc) { en = snode[wv][lane]; ea = sboxa[wv][lane]; eb = sboxb[wv][lane]; }
-                if (lane < fc) { snode[wv][fc - 1 - lane] = en; sboxa[wv][fc - 1 - lane] = ea; sboxb[wv][fc - 1 - lane] = eb; }
-                sp = fc;
-                node = 0;
-                while (sp > 0) {
-                    --sp;
-                    const float4 b0 = sboxa[wv][sp];
-                    const float2 b1 = sboxb[wv][sp];
-                    const float d = box_d2(xf, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y);
-                    em = __ballot(d <= bnd * kBoxSlack);
-                    if (em) { node = snode[wv][sp]; break; }
-                }
-                if (!node) em = 0ull;
-            }
-        }
-    }
+    // The loop body is three plain ifs in a row — if (node < P) the node step, if (at_leaf) the leaf
+    // scan, if (pop) the pop — with no else, no continue, no break, and one exit at the header, so
+    // that the keys and bnd are one loop-carried value each.  The loop holds divergent branches (the
+    // insertions), so the backend's control-flow structuriser rewrites all of it, and it turns
+    // `if (c) A else B` into `if (c) A; Flow; if (!c) B`: every value A writes gets a register of
+    // its own, undefined on the path around A.  The leaf scan's keys then could not share registers
+    // with the loop's, and all KL + 1 were copied at the leaf's entry and again at the back edge
+    // (profiles/r07_knn_issue/).  Around a plain if the bypass carries the loop's own value.
+    // at_leaf and pop (and bcast in scan_leaf) pass through empty asm pins: the optimiser would
+    // otherwise see that they are complementary / constant on each path and thread the three ifs
+    // back into the if/else + continue + break shape.
     while (em) {
+        int pop = 1;
+        int at_leaf = __builtin_amdgcn_readfirstlane(node >= P);
+        asm volatile("" : "+s"(at_leaf));
         if (node < P) {
             // one step descends `sw` binary levels at once: the 2^sw descendants' boxes sit in
             // the 2^(sw−1) consecutive records of the intermediate level (one scalar burst of
@@ -1082,6 +984,16 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             // fetched by vector loads into 48 VGPRs)
             const int unode = __builtin_amdgcn_readfirstlane(node);
             const kconst_f4* rec = (const kconst_f4*)t.nodes + 3 * ((size_t)unode << (sw - 1));
+            // lane k < 2^sw also fetches child k's own box (6 consecutive floats of the records) by a
+            // vector load: the push below then is ONE masked section — lane k writes child k's stack
+            // entry — instead of eight unrolled lane-0 pushes fed from the scalar records, and the 48
+            // record SGPRs die after the box tests (they were live to the last push, the cause of
+            // most scalar spills).  Issued before the scalar burst, consumed after the vote
+            float2 cb0 = make_float2(0.f, 0.f), cb1 = cb0, cb2 = cb0;
+            if (lane < nk) {
+                const float2* cp = reinterpret_cast<const float2*>(t.nodes + 3 * ((size_t)unode << (sw - 1))) + 3 * lane;
+                cb0 = cp[0]; cb1 = cp[1]; cb2 = cp[2];
+            }
             float4 R[3 * (kWideMax / 2)];
 #pragma unroll
             for (int k = 0; k < 3 * (kWideMax / 2); ++k) {
@@ -1102,30 +1014,36 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             }
             // descend into the child most lanes find nearest; stack the other wanted ones so that
             // they pop in Morton (index) order
+            // (its ballot is carried along by scalar selects: m[cstar] is an indexed register move)
             int cstar = -1, vbest = 0;
+            unsigned long long mstar = 0ull;
 #pragma unroll
             for (int k = 0; k < kWideMax; ++k) {
                 const int v = __popcll(__ballot(best == k));
-                if (m[k] && (cstar < 0 || v > vbest)) { cstar = k; vbest = v; }
+                if (m[k] && (cstar < 0 || v > vbest)) { cstar = k; vbest = v; mstar = m[k]; }
+            }
+            // the wanted children but cstar, pushed as the unrolled loop k = 7 … 0 did (child k above
+            // every wanted child > k, so they pop in Morton order): child k's slot is sp + the number
+            // of pushed children above k.  The divergent section stands alone, before the uniform
+            // updates: merged into their if, its join made sp, em, node and pop look divergent
+            unsigned wm = 0u;
+#pragma unroll
+            for (int k = 0; k < kWideMax; ++k) wm |= m[k] ? (1u << k) : 0u;
+            const unsigned pm = cstar >= 0 ? wm & ~(1u << cstar) : 0u;
+            if (lane < kWideMax && ((pm >> lane) & 1u)) {
+                const int pos = sp + __popc(pm >> (lane + 1));
+                snode[wv][pos] = (node << sw) + lane;
+                sboxa[wv][pos] = make_float4(cb0.x, cb0.y, cb1.x, cb1.y);
+                sboxb[wv][pos] = cb2;
             }
             if (cstar >= 0) {
-#pragma unroll
-                for (int k = kWideMax - 1; k >= 0; --k) {
-                    if (m[k] && k != cstar) {
-                        if (lane == 0) {
-                            const float4 a = R[3 * (k >> 1)], b = R[3 * (k >> 1) + 1], c = R[3 * (k >> 1) + 2];
-                            snode[wv][sp] = (node << sw) + k;
-                            sboxa[wv][sp] = (k & 1) ? make_float4(b.z, b.w, c.x, c.y) : make_float4(a.x, a.y, a.z, a.w);
-                            sboxb[wv][sp] = (k & 1) ? make_float2(c.z, c.w) : make_float2(b.x, b.y);
-                        }
-                        ++sp;
-                    }
-                }
-                em = m[cstar];
+                sp += __popc(pm);
+                em = mstar;
                 node = (node << sw) + cstar;
-                continue;
+                pop = 0;
             }
-        } else {
+        }
+        if (at_leaf) {
             ++n_leaf;
             const int leaf = node - P;
             float4 mine = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1151,17 +1069,21 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
 #endif
             scan_leaf(leaf, em, use_prev || gmask, mine);
         }
-        // pop: the stacked node's box is in LDS — re-check it against the shrunken lane bounds
-        node = 0;
-        while (sp > 0) {
-            --sp;
-            const float4 b0 = sboxa[wv][sp];
-            const float2 b1 = sboxb[wv][sp];
-            const float d = box_d2(xf, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y);
-            em = __ballot(d <= bnd * kBoxSlack);
-            if (em) { node = snode[wv][sp]; break; }
+        // pop: the stacked node's box is in LDS — re-check it against the shrunken lane bounds.  The
+        // flag is opaque to the optimiser (an empty pin), which would otherwise thread the leaf path
+        // straight into the pop and the descent straight to the back edge: see the loop's header
+        asm volatile("" : "+s"(pop));
+        if (pop) {
+            em = 0ull;
+            while (sp > 0 && !em) {
+                --sp;
+                const float4 b0 = sboxa[wv][sp];
+                const float2 b1 = sboxb[wv][sp];
+                const float d = box_d2(xf, b0.x, b0.y, b0.z, b0.w, b1.x, b1.y);
+                em = __ballot(d <= bnd * kBoxSlack);
+            }
+            if (em) node = snode[wv][sp];
         }
-        if (!node) break;
     }
     if (active && skip) wlist[slot] = wskip;   // a reused list stays in place
     if (active && !skip) {
@@ -1197,8 +1119,6 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                                  w1 = __ballot(active && full_() && thr_() > 1.0f);
         float wmax = active && full_() ? thr_() : 0.f;
         for (int o = 1; o < 64; o <<= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o));
-        unsigned sins = dbg_sparse_ins;
-        for (int o = 1; o < 64; o <<= 1) sins += __shfl_xor(sins, o);
         if (lane == 0) {
             const int w = bx * (kWaveBlock / 64) + wv;
             if (w < kDbgWaves) {
@@ -1206,7 +1126,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 r[0] = (unsigned)(dbg_t1 - dbg_t0); r[1] = (unsigned)(wall_clock64() - dbg_t1);
                 r[2] = n_leaf; r[3] = n_inner; r[4] = dbg_ev; r[5] = dbg_sparse; r[6] = dbg_bcast;
                 r[7] = __popcll(gl); r[8] = __popcll(wi); r[9] = __popcll(w1); r[10] = __float_as_uint(wmax);
-                r[11] = dbg_sparse_lanes; r[12] = sins; r[13] = dbg_ins;
+                r[11] = dbg_sparse_lanes; r[12] = dbg_listed_lv; r[13] = dbg_ins;
                 r[14] = dbg_seed_steps; r[15] = __builtin_amdgcn_readfirstlane(dbg_seed_pts);
             }
         }
@@ -2612,26 +2532,6 @@ __global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave(
 }
 
 template <int KL>
-__global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave_bfs(
-        TreeView t, const float4* __restrict__ spt, const unsigned* __restrict__ qperm, int N,
-        const double* __restrict__ pose, const int* __restrict__ done, KParams kp, const double* __restrict__ delta,
-        int* __restrict__ lists, float* __restrict__ wlist, float4* __restrict__ xref, float* __restrict__ nref,
-        int use_prev, unsigned long long* __restrict__ nbr_stats) {
-    knn_wave_body<KL, 3>(t, spt, qperm, N, pose, done, kp, delta, lists, wlist, xref, nref, use_prev, nbr_stats,
-                         (int)blockIdx.x);
-}
-
-template <int KL, int MODE>
-__global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave_m(
-        TreeView t, const float4* __restrict__ spt, const unsigned* __restrict__ qperm, int N,
-        const double* __restrict__ pose, const int* __restrict__ done, KParams kp, const double* __restrict__ delta,
-        int* __restrict__ lists, float* __restrict__ wlist, float4* __restrict__ xref, float* __restrict__ nref,
-        unsigned long long* __restrict__ nbr_stats) {
-    knn_wave_body<KL, MODE>(t, spt, qperm, N, pose, done, kp, delta, lists, wlist, xref, nref, 1, nbr_stats,
-                            (int)blockIdx.x, cmp_of(lists, N), cmp_count_of(lists, N));
-}
-
-template <int KL>
 __global__ __launch_bounds__(kWaveBlock) void k_knn_qwave(
         TreeView t, const float4* __restrict__ spt, const unsigned* __restrict__ qperm, int N,
         const double* __restrict__ pose, const int* __restrict__ done, KParams kp, const double* __restrict__ delta,
@@ -2735,33 +2635,6 @@ __global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave_b(const P
 }
 
 template <int KL>
-__global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave_bfsb(const PairDev* __restrict__ tab, KParams kp,
-                                                                             int use_prev, int npairs) {
-    int f, bx;
-    batch_block(kp.xcd, f, bx);
-    if (f >= npairs) return;
-    const PairDev A = device_view(tab + f);
-    if (use_qwave(kp, A.N) || bx >= knn_blocks_of(A.N, kp.packet)) return;
-    float4* xref = xref_dev(A.lists, A.N);
-    knn_wave_body<KL, 3>(A.t, A.spt, A.qperm, A.N, A.st.pose, A.st.done, kp, A.st.delta, A.lists,
-                         wlist_of<KL>(A.lists, A.N), xref, reinterpret_cast<float*>(xref + A.N), use_prev, A.stats, bx);
-}
-
-template <int KL, int MODE>
-__global__ __launch_bounds__(kWaveBlock) IMLS_KNN_ATTR void k_knn_wave_mb(const PairDev* __restrict__ tab, KParams kp,
-                                                                           int npairs) {
-    int f, bx;
-    batch_block(kp.xcd, f, bx);
-    if (f >= npairs) return;
-    const PairDev A = device_view(tab + f);
-    if (use_qwave(kp, A.N) || bx >= knn_blocks_of(A.N, kp.packet)) return;
-    float4* xref = xref_dev(A.lists, A.N);
-    knn_wave_body<KL, MODE>(A.t, A.spt, A.qperm, A.N, A.st.pose, A.st.done, kp, A.st.delta, A.lists,
-                            wlist_of<KL>(A.lists, A.N), xref, reinterpret_cast<float*>(xref + A.N), 1, A.stats, bx,
-                            cmp_of(A.lists, A.N), cmp_count_of(A.lists, A.N));
-}
-
-template <int KL>
 __global__ __launch_bounds__(kWaveBlock) void k_knn_qwave_b(const PairDev* __restrict__ tab, KParams kp, int use_prev,
                                                             int npairs) {
     int f, bx;
@@ -2810,14 +2683,7 @@ void launch_wave_batch(hipStream_t s, const PairDev* tab, int npairs, int maxN, 
     }
     if (any_large) {
         const int kb = knn_blocks_of(maxN, kp.packet);
-        if (it < IMLS_BFS_ITERS) {
-            k_knn_wave_bfsb<KL><<<dim3(kb, gy), kWaveBlock, 0, s>>>(tab, kp, use_prev, npairs);
-        } else if (use_prev && IMLS_COMPACT) {
-            k_knn_wave_mb<KL, 1><<<dim3(kb, gy), kWaveBlock, 0, s>>>(tab, kp, npairs);
-            k_knn_wave_mb<KL, 2><<<dim3(kb, gy), kWaveBlock, 0, s>>>(tab, kp, npairs);
-        } else {
-            k_knn_wave_b<KL><<<dim3(kb, gy), kWaveBlock, 0, s>>>(tab, kp, use_prev, npairs);
-        }
+        k_knn_wave_b<KL><<<dim3(kb, gy), kWaveBlock, 0, s>>>(tab, kp, use_prev, npairs);
     }
     k_finish_b<KL><<<dim3(wb, gy), kWaveBlock, 0, s>>>(tab, kp, it, npairs);
 }
@@ -2861,16 +2727,7 @@ void launch_wave(hipStream_t s, int blocks, const TreeView& t, const float4* spt
     else if (use_qwave(kp, N))
         k_knn_qwave<KL><<<(N + kWaveBlock / 64 - 1) / (kWaveBlock / 64), kWaveBlock, 0, s>>>(t, spt, qperm, N, pose, done, kp,
                                                                                           delta, lists, wlist, xref, nref, use_prev, stats);
-    else if (kp.bfs && IMLS_BFS_ITERS > 0)
-        k_knn_wave_bfs<KL><<<knn_blocks_of(N, kp.packet), kWaveBlock, 0, s>>>(t, spt, qperm, N, pose, done, kp, delta, lists,
-                                                                              wlist, xref, nref, use_prev, stats);
-    else if (use_prev && IMLS_COMPACT) {
-        // later iterations: reuse decided per lane, then packets of the compacted re-traversing slots
-        k_knn_wave_m<KL, 1><<<knn_blocks_of(N, kp.packet), kWaveBlock, 0, s>>>(t, spt, qperm, N, pose, done, kp, delta, lists,
-                                                                               wlist, xref, nref, stats);
-        k_knn_wave_m<KL, 2><<<knn_blocks_of(N, kp.packet), kWaveBlock, 0, s>>>(t, spt, qperm, N, pose, done, kp, delta, lists,
-                                                                               wlist, xref, nref, stats);
-    } else
+    else
         k_knn_wave<KL><<<knn_blocks_of(N, kp.packet), kWaveBlock, 0, s>>>(t, spt, qperm, N, pose, done, kp, delta, lists, wlist,
                                                                           xref, nref, use_prev, stats);
     if (marks) (void)hipEventRecord(marks[1], s);

@@ -1,8 +1,6 @@
 """Per-ICP-iteration medians of the projection / solve kernels from a rocprofv3 kernel trace of a
 one-pair-in-flight config-B run (stream order; an iteration ends at its k_finish).  The traversal of an
-iteration is every k_knn_wave* launch since the previous k_finish: the one-pass k_knn_wave (iteration
-0), or, from round 6, the reuse-decision launch k_knn_wave_m<KL, 1> + the compacted walk <KL, 2>
-(listed separately as prep / walk)."""
+iteration is every k_knn_wave launch since the previous k_finish."""
 import collections
 import csv
 import re
@@ -24,16 +22,10 @@ cur = collections.defaultdict(float)
 single = collections.defaultdict(list)
 for r in rows:
     n = r["Kernel_Name"]
-    if re.search(r"k_knn_wave_m<\d+, 1>", n):
-        cur["prep"] += dur(r)
-        cur["k_knn_wave"] += dur(r)
-    elif re.search(r"k_knn_wave_m<\d+, 2>", n):
-        cur["walk"] += dur(r)
-        cur["k_knn_wave"] += dur(r)
-    elif "k_knn_wave<" in n or "k_knn_wave(" in n:
+    if "k_knn_wave<" in n or "k_knn_wave(" in n:
         cur["k_knn_wave"] += dur(r)
     elif "k_finish<" in n or "k_finish(" in n:
-        for k in ("k_knn_wave", "prep", "walk"):
+        for k in ("k_knn_wave",):
             per_iter[k].append(cur.get(k, 0.0))
         per_iter["k_finish"].append(dur(r))
         cur.clear()
@@ -42,7 +34,7 @@ for r in rows:
                   "k_solve_small", "k_project_lane"):
             if k + "<" in n or k + "(" in n:
                 single[k].append(dur(r))
-for k in ("k_knn_wave", "prep", "walk", "k_finish"):
+for k in ("k_knn_wave", "k_finish"):
     a = np.array(per_iter.get(k, []))
     m = len(a) // iters * iters
     if not m:

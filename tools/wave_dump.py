@@ -11,7 +11,7 @@ pair = synth.make_pairs(1, "hdl64", map_scans=10, scene_seed=0, traj_seed=2000, 
 sd = torch.from_numpy(np.ascontiguousarray(synth.soa(pair.source))).cuda()
 td = torch.from_numpy(np.ascontiguousarray(synth.soa(pair.target))).cuda()
 cols = ["seed_t", "trav_t", "leaves", "inner", "bc_events", "sparse_lv", "bcast_lv", "greedy", "W_inf", "W>1", "Wmax",
-        "sp_lanes", "sp_ins", "bc_ins", "seed_steps", "seed_pts"]
+        "sp_lanes", "sp_listed_lv", "bc_ins", "seed_steps", "seed_pts"]
 for iters in [int(a) for a in sys.argv[1:]] or [1]:
     c = imls_icp.ImlsContext(config.bench_params(iters), device=0)
     c.set_target_device(td.data_ptr(), pair.target.size)
