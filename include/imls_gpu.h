@@ -463,6 +463,39 @@ int imls_sample_point_cloud(imls_ctx* ctx, const imls_sample_params* p, const fl
                             const float* last_xyz, size_t last_stride_floats, size_t m, int32_t* sampled_out,
                             size_t* n_sampled, float* bin_weights_out);
 
+/* ---- nearest-neighbour queries ---------------------------------------------------------- */
+/* Replaces a Nabo::NNSearchD::knn call (imls_icp.cpp:197, 372, 414, 605, 650;
+ * laser_odometry.cpp:348) with epsilon = 0 and SORT_RESULTS on the index the context already holds:
+ * the exact, radius-bounded, sorted k nearest neighbours of every query.
+ *   target: the current index — the last imls_set_target[_device], or the map FIFO after
+ *     imls_map_push[_device] (any max_queue_size); a deferred build is completed first.  An index is
+ *     the position in the NaN-filtered target (libnabo's column index; for the FIFO the filtered
+ *     concatenation, oldest scan first).
+ *   distance: d² = ((dx² + dy²) + dz²) in double from the float coordinates, no FMA.
+ *   accepted: d² <= max_radius² (inclusive; +inf = unbounded) and, without
+ *     IMLS_KNN_ALLOW_SELF_MATCH, d² > DBL_EPSILON.
+ *   rows: row i of idx_out / d2_out ([nq][k], row-major = libnabo's column-major k×nq) holds query
+ *     i's accepted neighbours ascending by (d², index); unfound slots hold idx −1, d² +inf;
+ *     found_out[i] (nullable) = filled slots.  A query with a non-finite coordinate gets an
+ *     all-unfound row (decided on the device; it never reaches the tree).
+ *   k in [1, 32] (the bound on search_number), else IMLS_ERR_UNSUPPORTED; k may exceed the target
+ *     size.  max_radius <= 0 or NaN, unknown flag bits, nq >= 2^31 → IMLS_ERR_ARG; no target, or a
+ *     frame pending (imls_register_frame_async / imls_register_frames_async not collected) →
+ *     IMLS_ERR_STATE; nq = 0 → IMLS_OK, nothing written.
+ * Sets of more than 262144 queries run as consecutive chunks of that size inside the call.
+ * IMLS_OPT_TRAVERSAL, IMLS_OPT_LEAF_SIZE and IMLS_OPT_FORCE_FALLBACK apply as to imls_project (every
+ * value gives the same rows).  The call reads the target only, in buffers of its own: the loaded
+ * source, the correspondences, the neighbour lists carried between ICP iterations, captured
+ * correspondences, the RANSAC rand() stream, traces and reject counters are untouched. */
+enum { IMLS_KNN_ALLOW_SELF_MATCH = 1 };      /* own constants; results are always sorted */
+/* host queries: point i at q_xyz + i*stride_floats (stride >= 3); host outputs; synchronises */
+int imls_knn(imls_ctx* ctx, const float* q_xyz, size_t stride_floats, size_t nq, int32_t k, double max_radius,
+             uint32_t flags, int32_t* idx_out, double* d2_out, int32_t* found_out);
+/* device queries SoA float32[3][nq], device outputs (d_found_out nullable); enqueued on the context
+ * stream, no host wait: collect after imls_synchronize (the query buffer may be reused then) */
+int imls_knn_device(imls_ctx* ctx, const float* d_q3, size_t nq, int32_t k, double max_radius, uint32_t flags,
+                    int32_t* d_idx_out, double* d_d2_out, int32_t* d_found_out);
+
 /* ---- runtime options ------------------------------------------------------------------- */
 /* No reference equivalent: the documented tuning parameters and test hooks of the GPU path, per
  * context (the library reads no environment variable except IMLS_DEBUG_HOST, a host-side trace).
@@ -502,7 +535,9 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * the last reset.  kernel: 0 = projection (all its kernels), 1 = index build (all its kernels),
  * 2 = solve chain, 3 = k_knn_wave (packet traversal) alone, 4 = k_finish (exact stage) alone,
  * 5 = k_ring_pca (imls_ring_normals_pca), 6 = k_major_avg (imls_sample_point_cloud, major_axis),
- * 7 = imls_scan_front_end (all its kernels).  enable: 0 off, 1 every kind above (the members of
+ * 7 = imls_scan_front_end (all its kernels), 8 = imls_knn / imls_knn_device (traversal, export and
+ * exact fallback of each chunk; the queries' ordering is not included, as the source's is not in 0;
+ * imls_knn_device's events are read by the next call that synchronises, e.g. imls_knn).  enable: 0 off, 1 every kind above (the members of
  * an imls_register_frames batch then build their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */

@@ -206,6 +206,48 @@ private:
     uint64_t reject_[IMLS_NUM_REJ] = {0, 0, 0, 0, 0, 0};
 };
 
+// Replaces a `Nabo::NNSearchD*` bound to the target (m_pTargetKDTree / p_target_KDtree): the knn
+// call sites imls_icp.cpp:197, 372, 414, 605, 650 and laser_odometry.cpp:348 keep their argument
+// lists.  Binds to a context that already holds the target (setTargetPointCloud / imls_set_target /
+// imls_map_push); the index stays on the GPU.
+class NNSearchHip {
+public:
+    // libnabo's option bits, declared here (no nabo.h needed).  Results are always sorted
+    // (SORT_RESULTS is implied); other bits — the reference's stray TOUCH_STATISTICS — are ignored.
+    enum SearchOptionFlags : unsigned { ALLOW_SELF_MATCH = 1, SORT_RESULTS = 2, TOUCH_STATISTICS = 4 };
+
+    explicit NNSearchHip(imls_ctx* ctx) : ctx_(ctx) {}
+    explicit NNSearchHip(const IMLSICPMatcherHip& m) : ctx_(m.context()) {}
+
+    // NNSearchD::knn(query, indices, dists2, k, epsilon, optionFlags, maxRadius) on raw storage:
+    // query 3×Q column-major doubles (an Eigen::MatrixXd's or VectorXd's data()), indices / dists2
+    // k×Q column-major — which is the ABI's row-major [Q][k], so nothing is transposed.  Unfound
+    // slots: index −1, dists2 +inf (libnabo's InvalidIndex / InvalidValue).  Returns the total
+    // number of neighbours found, as libnabo does.  The queries are narrowed to float: the
+    // reference's queries are float-valued doubles (points of a float cloud cast to double), for
+    // which the narrowing is exact.  epsilon != 0 (approximate search) is not offered: throws,
+    // citing IMLS_ERR_UNSUPPORTED.
+    unsigned long knn(const double* query, size_t Q, int* indices, double* dists2, int k, double epsilon = 0.0,
+                      unsigned optionFlags = 0, double maxRadius = INFINITY) const {
+        if (epsilon != 0.0)
+            throw std::runtime_error("imls_gpu call failed with status " + std::to_string((int)IMLS_ERR_UNSUPPORTED) +
+                                     ": NNSearchHip::knn is exact (epsilon must be 0)");
+        static_assert(sizeof(int) == sizeof(int32_t), "indices are int32");
+        std::vector<float> q(3 * Q);
+        for (size_t i = 0; i < 3 * Q; ++i) q[i] = (float)query[i];
+        std::vector<int32_t> found(Q);
+        const uint32_t flags = (optionFlags & ALLOW_SELF_MATCH) ? (uint32_t)IMLS_KNN_ALLOW_SELF_MATCH : 0u;
+        detail::check(imls_knn(ctx_, q.data(), 3, Q, k, maxRadius, flags, reinterpret_cast<int32_t*>(indices), dists2,
+                               found.data()), ctx_);
+        unsigned long total = 0;
+        for (size_t i = 0; i < Q; ++i) total += (unsigned long)found[i];
+        return total;
+    }
+
+private:
+    imls_ctx* ctx_;
+};
+
 namespace detail {
 template <class V>
 inline void flatten(const V& v, std::vector<double>& out) {

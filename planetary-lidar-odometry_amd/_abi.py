@@ -24,6 +24,7 @@ IMLS_NUM_REJ = 6
 (IMLS_OPT_TRAVERSAL, IMLS_OPT_LIST_REUSE, IMLS_OPT_TEMPORAL_SEED, IMLS_OPT_LEAF_SIZE, IMLS_OPT_FIRST_PACKET,
  IMLS_OPT_FIRST_PACKET_ITERS, IMLS_OPT_FIRST_PACKET_BATCHED, IMLS_OPT_TV_SKIN, IMLS_OPT_FORCE_FALLBACK) = range(9)
 IMLS_TRAVERSAL_AUTO, IMLS_TRAVERSAL_PACKETS, IMLS_TRAVERSAL_WAVE_PER_QUERY, IMLS_TRAVERSAL_LANE = 0, 1, 2, 3
+IMLS_KNN_ALLOW_SELF_MATCH = 1   # imls_knn flags (results are always sorted)
 OPTION_IDS = {"traversal": IMLS_OPT_TRAVERSAL, "list_reuse": IMLS_OPT_LIST_REUSE,
               "temporal_seed": IMLS_OPT_TEMPORAL_SEED, "leaf_size": IMLS_OPT_LEAF_SIZE,
               "first_packet": IMLS_OPT_FIRST_PACKET, "first_packet_iters": IMLS_OPT_FIRST_PACKET_ITERS,
@@ -226,6 +227,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "imls_captured_correspondences": (C.c_int, [VP, C.c_int, SZ, VP, VP, VP, VP, P(SZ)]),
         "imls_timing_origin": (C.c_int, [VP]),
         "imls_timing_intervals": (C.c_int, [VP, C.c_int, VP, SZ, P(SZ)]),
+        "imls_knn": (C.c_int, [VP, VP, SZ, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
+        "imls_knn_device": (C.c_int, [VP, VP, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -248,7 +251,7 @@ ABI_SYMBOLS = (
     "imls_register_frames", "imls_register_frames_async", "imls_register_frames_result",
     "imls_default_front_params", "imls_scan_front_end", "imls_enable_stats", "imls_set_defer",
     "imls_timing_origin", "imls_timing_intervals", "imls_capture_correspondences",
-    "imls_captured_correspondences", "imls_set_option", "imls_get_option",
+    "imls_captured_correspondences", "imls_set_option", "imls_get_option", "imls_knn", "imls_knn_device",
 )
 
 _LIB = None

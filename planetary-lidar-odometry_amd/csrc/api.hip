@@ -139,7 +139,7 @@ void release_retired(int device) {
 }
 }  // namespace imlsgpu
 
-constexpr int kTimingKinds = 8;   // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end
+constexpr int kTimingKinds = 9;   // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query
 
 // Runtime options of a context (imls_set_option; include/imls_gpu.h documents each): the validated
 // tuning parameters and test hooks.  Nothing is read from the environment.
@@ -218,6 +218,11 @@ struct imls_ctx {
     DevBuf pca_mem;                       // imls_ring_normals_pca scratch (upstream producer)
     DevBuf sample_mem;                    // imls_sample_point_cloud scratch
     DevBuf front_mem;                     // imls_scan_front_end scratch
+    // imls_knn / imls_knn_device: buffers of their own (one chunk of ≤ kKnnChunk queries), so a query
+    // leaves the loaded source, its order, the correspondences and the neighbour lists alone —
+    // queries (xyz, non-finite flag), their Morton order + the sort's scratch, the list block,
+    // the deferred-query counts + lists, the identity pose, and the host form's staging (upload, rows)
+    DevBuf knn_q, knn_perm, knn_scratch, knn_lists, knn_fb, knn_pose, knn_up, knn_out;
     size_t n_target_in = 0;               // input size of the last set_target (tensor arrays match it)
     bool has_tensors = false;
     Options opt;                          // imls_set_option
@@ -1272,7 +1277,8 @@ void imls_destroy(imls_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->ustream) (void)hipStreamSynchronize(c->ustream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&c->cap_mem, &c->front_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
+    DevBuf* bufs[] = {&c->knn_q, &c->knn_perm, &c->knn_scratch, &c->knn_lists, &c->knn_fb, &c->knn_pose, &c->knn_up, &c->knn_out,
+                      &c->cap_mem, &c->front_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
                       &c->upload_t, &c->spt, &c->snr, &c->sscratch,
                       &c->upload_s, &c->cs, &c->cd, &c->cn, &c->solve_mem, &c->trace_mem, &c->stats, &c->rows_d, &c->pose_tmp};
     for (DevBuf* b : bufs)
@@ -2485,6 +2491,107 @@ int imls_sample_point_cloud(imls_ctx* c, const imls_sample_params* p, const floa
     if (mk && rc == IMLS_OK && p->method != IMLS_SAMPLE_MAJOR_AXIS) c->ev_pairs[6].pop_back();   // no kernel recorded
     if (c->timing) harvest_timing(c);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nearest-neighbour queries on the current index (Nabo::NNSearchD::knn, epsilon 0, SORT_RESULTS)
+// ---------------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+
+// argument and state checks shared by both forms; completes a pending target build
+int knn_check(imls_ctx* c, size_t nq, int32_t k, double max_radius, uint32_t flags) {
+    if (k < 1 || k > 32) return fail(c, IMLS_ERR_UNSUPPORTED, "knn: k must be in [1, 32] (k = " + std::to_string(k) + ")");
+    if (!(max_radius > 0.0)) return fail(c, IMLS_ERR_ARG, "knn: max_radius must be > 0 (+inf: unbounded)");
+    if (flags & ~(uint32_t)IMLS_KNN_ALLOW_SELF_MATCH) return fail(c, IMLS_ERR_ARG, "knn: unknown flag bits");
+    if (nq >= ((size_t)1 << 31)) return fail(c, IMLS_ERR_ARG, "knn: nq must be < 2^31");
+    if (c->pending || c->batch_member) return fail(c, IMLS_ERR_STATE, "collect the frame first (imls_register_frame_result)");
+    if (int rc = finish_target(c)) return rc;
+    if (!c->has_target) return fail(c, IMLS_ERR_STATE, "knn: set_target or map_push first");
+    return IMLS_OK;
+}
+
+// One chunk of n ≤ kKnnChunk queries (component d of query i at d_src[i·pstride + d·cstride], device)
+// → device rows; everything is enqueued on the context stream, nothing waits.
+int knn_chunk(imls_ctx* c, const float* d_src, size_t pstride, size_t cstride, int n, int32_t k, double max_radius,
+              uint32_t flags, int32_t* d_idx, double* d_d2, int32_t* d_found) {
+    const size_t nreg = ((size_t)n + 63) / 64, fb_off = (nreg + 63) / 64 * 64;
+    if (!grow(c->knn_q, (size_t)n * 16) || !grow(c->knn_lists, knn_list_bytes(n)) ||
+        !grow(c->knn_fb, (fb_off + nreg * 64) * 4) || !grow(c->knn_pose, 256))
+        return fail(c, IMLS_ERR_DEVICE, "hipMalloc (knn)");
+    const TreeView t = tree_view(c);
+    knn_prepare(c->stream, t, d_src, pstride, cstride, n, (float4*)c->knn_q.p, (double*)c->knn_pose.p);
+    if (int rc = query_order(c->stream, (const float4*)c->knn_q.p, n, t.qparams, c->knn_scratch, c->knn_perm, c->err)) return rc;
+    KnnArgs a{};
+    a.K = k;
+    a.r2 = max_radius * max_radius;
+    a.allow_self = (flags & IMLS_KNN_ALLOW_SELF_MATCH) ? 1 : 0;
+    a.qwave = c->kp.qwave;
+    a.force_fb = c->kp.force_fb;
+    int slot;
+    timed_begin(c, 8, slot);
+    launch_knn(c->stream, t, (const float4*)c->knn_q.p, (const unsigned*)c->knn_perm.p, n, (const double*)c->knn_pose.p, a,
+               c->lane_mode, (int*)c->knn_lists.p, (unsigned*)c->knn_fb.p + fb_off, (unsigned*)c->knn_fb.p, d_idx, d_d2,
+               d_found);
+    timed_end(c, 8, slot);
+    if (hipGetLastError() != hipSuccess) return fail(c, IMLS_ERR_DEVICE, "knn launch failed");
+    return IMLS_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int imls_knn(imls_ctx* c, const float* q_xyz, size_t stride_floats, size_t nq, int32_t k, double max_radius, uint32_t flags,
+             int32_t* idx_out, double* d2_out, int32_t* found_out) {
+    if (!c) return IMLS_ERR_ARG;
+    if (int rc = check_device(c)) return rc;
+    if (int rc = knn_check(c, nq, k, max_radius, flags)) return rc;
+    if (nq == 0) return IMLS_OK;
+    if (!q_xyz || !idx_out || !d2_out || stride_floats < 3) return fail(c, IMLS_ERR_ARG, "knn: null array or stride < 3");
+    std::vector<float> pack;
+    for (size_t c0 = 0; c0 < nq; c0 += kKnnChunk) {
+        const int n = (int)std::min(nq - c0, (size_t)kKnnChunk);
+        const float* src = q_xyz + c0 * stride_floats;
+        if (stride_floats != 3) {
+            pack.resize((size_t)n * 3);
+            for (int i = 0; i < n; ++i)
+                for (int d = 0; d < 3; ++d) pack[(size_t)i * 3 + d] = src[(size_t)i * stride_floats + d];
+            src = pack.data();
+        }
+        const size_t bi = ((size_t)n * k * 4 + 255) / 256 * 256, bd = ((size_t)n * k * 8 + 255) / 256 * 256;
+        if (!grow(c->knn_up, (size_t)n * 12) || !grow(c->knn_out, bi + bd + (size_t)n * 4))
+            return fail(c, IMLS_ERR_DEVICE, "hipMalloc (knn staging)");
+        int32_t* d_idx = (int32_t*)c->knn_out.p;
+        double* d_d2 = (double*)((char*)c->knn_out.p + bi);
+        int32_t* d_found = (int32_t*)((char*)c->knn_out.p + bi + bd);
+        if (hipMemcpyAsync(c->knn_up.p, src, (size_t)n * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return fail(c, IMLS_ERR_DEVICE, "knn: query upload failed");
+        if (int rc = knn_chunk(c, (const float*)c->knn_up.p, 3, 1, n, k, max_radius, flags, d_idx, d_d2, d_found)) return rc;
+        hipMemcpyAsync(idx_out + c0 * k, d_idx, (size_t)n * k * 4, hipMemcpyDeviceToHost, c->stream);
+        hipMemcpyAsync(d2_out + c0 * k, d_d2, (size_t)n * k * 8, hipMemcpyDeviceToHost, c->stream);
+        if (found_out) hipMemcpyAsync(found_out + c0, d_found, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+        // (per chunk: the staging buffers and `pack` are reused by the next one)
+        if (hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(c, IMLS_ERR_DEVICE, std::string("knn: ") + hipGetErrorString(hipGetLastError()));
+    }
+    harvest_timing(c);
+    return IMLS_OK;
+}
+
+int imls_knn_device(imls_ctx* c, const float* d_q3, size_t nq, int32_t k, double max_radius, uint32_t flags,
+                    int32_t* d_idx_out, double* d_d2_out, int32_t* d_found_out) {
+    if (!c) return IMLS_ERR_ARG;
+    if (int rc = check_device(c)) return rc;
+    if (int rc = knn_check(c, nq, k, max_radius, flags)) return rc;
+    if (nq == 0) return IMLS_OK;
+    if (!d_q3 || !d_idx_out || !d_d2_out) return fail(c, IMLS_ERR_ARG, "knn: null array");
+    for (size_t c0 = 0; c0 < nq; c0 += kKnnChunk) {
+        const int n = (int)std::min(nq - c0, (size_t)kKnnChunk);
+        if (int rc = knn_chunk(c, d_q3 + c0, 1, nq, n, k, max_radius, flags, d_idx_out + c0 * k, d_d2_out + c0 * k,
+                               d_found_out ? d_found_out + c0 : nullptr))
+            return rc;
+    }
+    return IMLS_OK;
 }
 
 int imls_enable_stats(imls_ctx* c, int enable) {

@@ -496,8 +496,10 @@ constexpr int kMortonSortLo = 0;
 // is double-buffered (round 6: the plain form ended in two copy-back launches of keys and values);
 // *perm_out = the buffer holding the permutation — perm's own storage when the caller needs it there
 // (need_in_perm: one device copy if the sort left it in scratch), else possibly scratch.
+// qp_fixed: a quantisation given by the caller (device, [4]) instead of the points' own bbox — the
+// kNN queries are keyed in the target's frame (query_order).
 int morton_perm(hipStream_t s, const float4* pts, int n, DevBuf& scratch, DevBuf& perm, std::string& err,
-                DevBuf* lkeys = nullptr, int B = 0, const unsigned** perm_out = nullptr) {
+                DevBuf* lkeys = nullptr, int B = 0, const unsigned** perm_out = nullptr, const float* qp_fixed = nullptr) {
     size_t cub_bytes = 0;
     {
         hipcub::DoubleBuffer<unsigned long long> kq(nullptr, nullptr);
@@ -521,9 +523,13 @@ int morton_perm(hipStream_t s, const float4* pts, int n, DevBuf& scratch, DevBuf
     if (lkeys && !ensure(*lkeys, (size_t)L * 8 + 16, err)) return IMLS_ERR_DEVICE;
     if (lkeys) qp = (float*)((unsigned long long*)lkeys->p + L);   // qparams live after the keys
     (void)cnt;
-    int nb = std::min(bb_parts, (int)grid_for(n));
-    k_bbox_partial<<<nb, kBlock, 0, s>>>(pts, n, bbpart);
-    k_bbox_final<<<1, kBlock, 0, s>>>(bbpart, nb, bbox, qp);
+    if (qp_fixed) {
+        qp = const_cast<float*>(qp_fixed);
+    } else {
+        int nb = std::min(bb_parts, (int)grid_for(n));
+        k_bbox_partial<<<nb, kBlock, 0, s>>>(pts, n, bbpart);
+        k_bbox_final<<<1, kBlock, 0, s>>>(bbpart, nb, bbox, qp);
+    }
     k_morton<<<grid_for(n), kBlock, 0, s>>>(pts, n, qp, k0, v0);
     unsigned long long* kcur;
     unsigned* vcur;
@@ -689,6 +695,14 @@ int source_order(hipStream_t s, int N, DevBuf& spt, DevBuf& scratch, DevBuf& qpe
         return small_source_order(s, (const float4*)spt.p, N, (unsigned*)qperm.p, err);
     }
     return morton_perm(s, (const float4*)spt.p, N, scratch, qperm, err);
+}
+
+// The kNN queries' order (imls_knn): the source path's keys and sort under the TARGET's quantisation
+// qp (TreeView::qparams) — a query outside the target's box clamps to its border instead of
+// stretching a box of the queries' own, so a few far queries do not cost the others their coherence.
+int query_order(hipStream_t s, const float4* pts, int n, const float* qp, DevBuf& scratch, DevBuf& perm, std::string& err) {
+    if (n <= 0) return IMLS_OK;
+    return morton_perm(s, pts, n, scratch, perm, err, nullptr, 0, nullptr, qp);
 }
 
 // ---------------------------------------------------------------------------------------------

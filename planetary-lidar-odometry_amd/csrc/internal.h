@@ -308,6 +308,8 @@ int build_target_tree(hipStream_t s, int M, int bucket, DevBuf& lkeys, DevBuf& t
                       DevBuf& nodes, DevBuf& scratch, DevBuf& treescratch, DevBuf& permbuf, int* P_out, int* levels_out,
                       std::string& err);
 int source_order(hipStream_t s, int N, DevBuf& spt, DevBuf& scratch, DevBuf& qperm, std::string& err);
+// the kNN queries' order (imls_knn): Morton keys under the target's quantisation qp (device, [4])
+int query_order(hipStream_t s, const float4* pts, int n, const float* qp, DevBuf& scratch, DevBuf& perm, std::string& err);
 // a small frame's source order (≤ kSmallOrderN points) in one launch — the same permutation
 constexpr int kSmallOrderN = 2048;
 int small_source_order(hipStream_t s, const float4* pts, int N, unsigned* perm, std::string& err);
@@ -385,6 +387,31 @@ __host__ __device__ inline float4* xref_of(int* lists, int N) {
 inline size_t prevnn_bytes(int N) {
     return ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256 + ((size_t)N * 20 + 255) / 256 * 256 + 512;
 }
+// Public kNN query (imls_knn / imls_knn_device): the same two stages over a query set of its own.
+// knn_prepare: queries (component c of point i at src[i·pstride + c·cstride]) → qpt[n] (xyz, flag:
+// a non-finite query is parked at the target's box corner with flag 1 — the tree never sees a NaN
+// — and gets an all-unfound row), and the identity pose the traversal kernels read.
+void knn_prepare(hipStream_t s, const TreeView& t, const float* src, size_t pstride, size_t cstride, int n, float4* qpt,
+                 double* pose);
+// Stage 1 (k_knn_wave / k_knn_qwave, unchanged) at the identity pose, then k_knn_export and the exact
+// k_knn_export_lane over its deferred queries; lane_mode: every query through k_knn_export_lane.
+// Outputs: rows [n][K] of (filtered index, fp64 d²) ascending by (d², index), unfound slots (−1, +∞),
+// found[n] (nullable).  lists: knn_list_bytes(n) bytes; fb_count / fb_list as k_finish's.
+struct KnnArgs {
+    int K;
+    double r2;                         // acceptance: d² ≤ r2 (+∞: unbounded)
+    int allow_self;                    // 0: entries with d² ≤ DBL_EPSILON are dropped
+    int qwave, force_fb;               // KParams::qwave / force_fb
+};
+void launch_knn(hipStream_t s, const TreeView& t, const float4* qpt, const unsigned* qperm, int n, const double* pose,
+                const KnnArgs& a, int lane_mode, int* lists, unsigned* fb_list, unsigned* fb_count, int32_t* idx_out,
+                double* d2_out, int32_t* found_out);
+// list block of n kNN queries: positions [kMaxKL + 1][n] (the last row: worst keys), xref, nref
+// (the traversal's Verlet outputs, unread here), the deferred queries' search caps [n]
+inline size_t knn_list_bytes(int n) { return prevnn_bytes(n) + ((size_t)n * 4 + 255) / 256 * 256; }
+inline float* knn_caps_of(int* lists, int n) { return reinterpret_cast<float*>(reinterpret_cast<char*>(lists) + prevnn_bytes(n)); }
+constexpr int kKnnChunk = 1 << 18;     // queries per launch sequence of imls_knn (larger sets: consecutive chunks)
+
 constexpr int kStatSkipped = 6;   // nbr_stats slot: lanes whose list was reused without traversal
 int project_blocks(int N);
 // k_finish: the exact stage one lane per query (0) or one quad per query (1: round 6, measured slower —

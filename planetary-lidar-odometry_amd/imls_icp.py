@@ -217,6 +217,32 @@ class ImlsContext:
         k = nv.value
         return x[:k], y[:k], n[:k], idx[:k], rej
 
+    # -- nearest-neighbour queries (Nabo::NNSearchD::knn, epsilon 0, SORT_RESULTS) ---------------
+    def knn(self, queries, k: int, max_radius: float = np.inf, allow_self_match: bool = True):
+        """The exact k nearest target points of every query within max_radius (imls_knn): queries
+        (nq, >=3) — the first three columns are xyz.  Returns (idx (nq, k) int32 — positions in the
+        NaN-filtered target, -1 unfound; d2 (nq, k) float64 — +inf unfound; found (nq,) int32), each
+        row ascending by (d2, idx)."""
+        q = np.asarray(queries)
+        if q.ndim != 2 or q.shape[1] < 3:
+            raise ValueError("queries must be (nq, >=3)")
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        nq, k = q.shape[0], int(k)
+        rows = max(k, 0)
+        idx = np.full((nq, rows), -1, np.int32); d2 = np.full((nq, rows), np.inf); found = np.zeros(nq, np.int32)
+        flags = _abi.IMLS_KNN_ALLOW_SELF_MATCH if allow_self_match else 0
+        self._check(self.lib.imls_knn(self.ctx, _ptr(q), q.shape[1], nq, k, float(max_radius), flags,
+                                      _ptr(idx), _ptr(d2), _ptr(found)))
+        return idx, d2, found
+
+    def knn_device(self, q_ptr: int, nq: int, k: int, max_radius: float, allow_self_match: bool,
+                   idx_ptr: int, d2_ptr: int, found_ptr: int = 0):
+        """imls_knn_device: queries SoA float32[3][nq] and outputs ([nq][k] int32 / float64, [nq] int32
+        or 0) on the device; enqueued on the context stream — collect after synchronize()."""
+        flags = _abi.IMLS_KNN_ALLOW_SELF_MATCH if allow_self_match else 0
+        self._check(self.lib.imls_knn_device(self.ctx, C.c_void_p(q_ptr), int(nq), int(k), float(max_radius), flags,
+                                             C.c_void_p(idx_ptr), C.c_void_p(d2_ptr), C.c_void_p(found_ptr or 0)))
+
     def solve(self):
         D = np.zeros(16); ok = C.c_int()
         self._check(self.lib.imls_solve(self.ctx, _ptr(D), C.byref(ok)))
