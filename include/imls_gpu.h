@@ -238,6 +238,29 @@ int imls_map_push(imls_ctx* ctx, const float* xyz, const float* nrm, size_t n, s
  * (count-less with imls_set_defer on) or until the context's stream has passed the push; raising
  * max_queue_size afterwards needs a fresh push.  Larger FIFOs copy the scan into a FIFO slot. */
 int imls_map_push_device(imls_ctx* ctx, const float* d_soa6, size_t n, size_t* n_map);
+/* Scan-to-model maps (no reference equivalent: accumulateTargetCloud's TransformToEnd calls are
+ * commented out, laser_odometry.cpp:116-136, so the reference's multi-scan map mixes sensor frames).
+ * As imls_map_push[_device], except that the scan enters the FIFO expressed in a map frame:
+ * pose = map ← scan.  The NaN / Inf filter tests the point as given; a kept point is stored as
+ *   float(((T[r][0]·x + T[r][1]·y) + T[r][2]·z) + T[r][3])   per row r, in double, no contraction
+ * (the arithmetic of the registration's own source transform) and its normal is ALWAYS rotated the
+ * same way (no translation) and rounded to float, whatever params.transform_normal says: a map whose
+ * normals stayed in another frame would be wrong.  The last row of `pose` is not read.  The pose is
+ * copied at the call (also under imls_set_defer); a non-finite entry → IMLS_ERR_ARG.  An identity
+ * pose IS the plain push (same bits).  With the incremental index (max_queue_size 2…31) only the new
+ * scan is transformed, inside its filter's scatter pass: older entries are neither moved, re-sorted
+ * nor re-keyed.  With max_queue_size 1 or ≥ 32 the FIFO slot receives the transformed scan (a
+ * non-identity pose at queue 1 therefore copies the device scan; it is not indexed in place). */
+int imls_map_push_posed(imls_ctx* ctx, const float* xyz, const float* nrm, size_t n, size_t stride_floats,
+                        const double pose[16], size_t* n_map);
+int imls_map_push_posed_device(imls_ctx* ctx, const float* d_soa6, size_t n, const double pose[16], size_t* n_map);
+/* Re-expresses every FIFO entry in a new map frame (pose = new ← old): the same arithmetic applied
+ * to the stored floats, one elementwise kernel per entry; the index is rebuilt at its next use (the
+ * incremental index drops its quantisation frame and re-keys every run).  For long runs: with float
+ * storage the map should stay near the sensor.  IMLS_ERR_STATE while a registration is pending, or
+ * when the FIFO's scan was indexed in place (max_queue_size 1, plain or identity device push: the
+ * data is the caller's).  An empty FIFO or an identity pose is a no-op. */
+int imls_map_rebase(imls_ctx* ctx, const double pose[16]);
 int imls_map_clear(imls_ctx* ctx);
 /* FIFO entries and their total point count (before the NaN filter). */
 int imls_map_size(imls_ctx* ctx, size_t* entries, size_t* points);
@@ -289,6 +312,14 @@ int imls_solve_correspondences(imls_ctx* ctx, int32_t method, const double* s, c
  * first *iters_run are meaningful. */
 int imls_register_frame(imls_ctx* ctx, double pose_out[16], int* iters_run, int* status,
                         imls_iter_trace* trace);
+/* The starting rPose of every later imls_register_frame[_async], and of this context's member of
+ * imls_register_frames[_async], in place of I (each frame of a batch starts from its own context's
+ * pose); NULL restores identity.  Sticky until changed; copied at the call; a non-finite entry →
+ * IMLS_ERR_ARG.  Only the start changes: the loop, its trace (pose = Δ·rPose), the convergence test
+ * and the too-few / solve-failed exits ("pose kept" = the initial pose at iteration 0) are the same.
+ * With a map kept in a fixed map frame (imls_map_push_posed) this is the predicted pose of the
+ * scan in that frame.  imls_register_batch keeps I. */
+int imls_set_initial_pose(imls_ctx* ctx, const double pose[16]);
 /* Asynchronous form: enqueue on the context stream and return; collect with
  * imls_register_frame_result (which synchronises the stream). */
 int imls_register_frame_async(imls_ctx* ctx);

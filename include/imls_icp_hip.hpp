@@ -181,6 +181,25 @@ public:
         return imls_register_frame(ctx_, pose_out, iters_run, status, nullptr);
     }
 
+    // Scan-to-model maps (imls_gpu.h): replaces accumulateTargetCloud(newCloud, max_queue_size, …) +
+    // the next setTargetPointCloud(accumulatedTargetCloud) with a FIFO kept in one map frame.  `pose`
+    // (row-major 4×4, map ← scan) is the scan's registered pose in that frame; the cloud is not
+    // modified.  Returns the map size after the NaN filter.
+    template <class CloudPtr>
+    size_t mapPushPosed(const CloudPtr& cloud, const double pose[16]) {
+        size_t n_map = 0;
+        const size_t n = cloud->size();
+        const float* x = n ? &cloud->points[0].x : nullptr;
+        const float* nx = n ? &cloud->points[0].normal_x : nullptr;
+        detail::check(imls_set_params(ctx_, &params_), ctx_);
+        detail::check(imls_map_push_posed(ctx_, x, nx, n, n ? stride(*cloud) : 6, pose, &n_map), ctx_);
+        return n_map;
+    }
+    // every FIFO entry re-expressed under `pose` (new ← old map frame)
+    void mapRebase(const double pose[16]) { detail::check(imls_map_rebase(ctx_, pose), ctx_); }
+    // registerFrame starts at rPose = pose (the scan's predicted pose in the map frame); nullptr = I
+    void setInitialPose(const double* pose) { detail::check(imls_set_initial_pose(ctx_, pose), ctx_); }
+
     const uint64_t* rejectCounters() const { return reject_; }
     const imls_params& params() const { return params_; }
 

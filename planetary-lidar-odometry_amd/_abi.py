@@ -218,6 +218,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "imls_set_rng_state": (C.c_int, [VP, VP]),
         "imls_map_push": (C.c_int, [VP, VP, VP, SZ, SZ, P(SZ)]),
         "imls_map_push_device": (C.c_int, [VP, VP, SZ, P(SZ)]),
+        "imls_map_push_posed": (C.c_int, [VP, VP, VP, SZ, SZ, VP, P(SZ)]),
+        "imls_map_push_posed_device": (C.c_int, [VP, VP, SZ, VP, P(SZ)]),
+        "imls_map_rebase": (C.c_int, [VP, VP]),
+        "imls_set_initial_pose": (C.c_int, [VP, VP]),
         "imls_map_clear": (C.c_int, [VP]),
         "imls_map_size": (C.c_int, [VP, P(SZ), P(SZ)]),
         "imls_set_defer": (C.c_int, [VP, C.c_int]),
@@ -252,6 +256,7 @@ ABI_SYMBOLS = (
     "imls_default_front_params", "imls_scan_front_end", "imls_enable_stats", "imls_set_defer",
     "imls_timing_origin", "imls_timing_intervals", "imls_capture_correspondences",
     "imls_captured_correspondences", "imls_set_option", "imls_get_option", "imls_knn", "imls_knn_device",
+    "imls_set_initial_pose", "imls_map_push_posed", "imls_map_push_posed_device", "imls_map_rebase",
 )
 
 _LIB = None

@@ -197,6 +197,8 @@ struct imls_ctx {
     unsigned* h_fifo_clamp = nullptr;     // pinned: points outside the frame at the last build
     DevBuf fifo_dev;                      // fq[4] | clamp counter
     bool fq_valid = false;
+    // imls_set_initial_pose: rPose at the start of every later registration (identity by default)
+    double init_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     std::vector<int> merged_ids;          // runs in the merged order, oldest first
     DevBuf mkey[2], mval[2];
     int mcur = 0, m_n = 0;
@@ -1174,11 +1176,19 @@ int check_device(imls_ctx* c) {
 
 // One frame's prologue / epilogue as one launch each (round 4: the lone-frame latency paid ~11 µs
 // for an H2D pose copy, five fills and four D2H copies around the 20 iterations).
+// (rPose starts at the context's initial pose — imls_set_initial_pose, identity by default — a
+// launch argument)
+struct Pose16 { double T[16]; };
+Pose16 init_pose_of(const imls_ctx* c) {
+    Pose16 p;
+    std::memcpy(p.T, c->init_pose, sizeof(p.T));
+    return p;
+}
 __global__ void k_frame_init(double* __restrict__ pose, int* __restrict__ done, int* __restrict__ status,
                              int* __restrict__ iters, unsigned long long* __restrict__ trace, int trace_words,
-                             unsigned long long* __restrict__ stats) {
+                             unsigned long long* __restrict__ stats, const Pose16 init) {
     const int t = threadIdx.x;
-    if (t < 16) pose[t] = (t % 5 == 0) ? 1.0 : 0.0;
+    if (t < 16) pose[t] = init.T[t];
     if (t < 4) { done[t] = 0; status[t] = 0; iters[t] = 0; }
     if (t < 16) stats[t] = 0ull;
     for (int k = t; k < trace_words; k += blockDim.x) trace[k] = 0ull;
@@ -1649,13 +1659,45 @@ int fifo_build(imls_ctx* c) {
 
 }  // namespace
 
+// The concatenation of the FIFO's raw scans (max_queue_size 1 or ≥ kMaxFifoRuns) as the target.
+static int map_assemble(imls_ctx* c, size_t* n_map) {
+    for (const auto& e : c->fifo)     // a scan indexed in place (max_queue_size was 1) is not held
+        if (e.ghost && e.n > 0) return fail(c, IMLS_ERR_STATE, "map FIFO holds a scan pushed with max_queue_size 1 (not kept): push again");
+    const size_t M = c->map_points;
+    if (M == 0) {                     // empty map (max_queue_size 0 or empty scans): no target
+        c->tgt_pending = false;
+        c->has_target = false;
+        c->has_corr = false;
+        c->M = 0;
+        if (n_map) *n_map = 0;
+        return IMLS_OK;
+    }
+    for (const auto& e : c->fifo)     // one non-empty entry (max_queue_size 1): index it in place
+        if (e.n == M) return do_set_target(c, (const float*)e.buf.p, M, n_map);
+    if (!grow(c->macc, M * 24)) return fail(c, IMLS_ERR_DEVICE, "hipMalloc (map)");
+    size_t off = 0;
+    for (const auto& e : c->fifo) {
+        if (e.n == 0) continue;
+        if (hipMemcpy2DAsync((float*)c->macc.p + off, M * 4, e.buf.p, e.n * 4, e.n * 4, 6, hipMemcpyDeviceToDevice,
+                             c->stream) != hipSuccess)
+            return fail(c, IMLS_ERR_DEVICE, "map assembly copy");
+        off += e.n;
+    }
+    return do_set_target(c, (const float*)c->macc.p, M, n_map);
+}
+
+// `pose` (nullable = the plain push): map ← scan.  The scan enters the FIFO in the map frame — the
+// incremental index transforms it inside its NaN filter's scatter pass (filter_async); the raw-scan
+// modes (queue 1, concatenation) write the slot's copy transformed (a device scan: in place of the
+// plain device-to-device copy; a host scan: over its upload).  The pose is a launch argument, so it
+// is copied at the call.
 static int map_push(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, const float* d_soa6,
-                    size_t* n_map) {
+                    size_t* n_map, const Pose12* pose = nullptr) {
     if (n > (size_t)0x7fffffff) return fail(c, IMLS_ERR_ARG, "scan too large");
     // max_queue_size 1 with a device scan (the shipped config, device frames): the map IS this
     // scan, dropped at the next push — index it where it lies (its NaN filter reads it on this
-    // stream, as the slot copy would), no FIFO copy
-    if (d_soa6 && c->P.max_queue_size == 1) {
+    // stream, as the slot copy would), no FIFO copy.  (A posed scan needs its transformed copy.)
+    if (d_soa6 && c->P.max_queue_size == 1 && !pose) {
         for (auto& e : c->fifo)
             if (!e.ghost) c->slot_pool.push_back(e);
         c->fifo.clear();
@@ -1700,18 +1742,21 @@ static int map_push(imls_ctx* c, const float* xyz, const float* nrm, size_t n, s
         const float* raw = d_soa6;
         if (!d_soa6 || !inc) {            // the incremental index filters a device scan where it lies
             if (!grow(sl.buf, n * 24)) { c->slot_pool.push_back(sl); return fail(c, IMLS_ERR_DEVICE, "hipMalloc (map slot)"); }
-            if (d_soa6) {
+            if (d_soa6 && pose && !inc) {
+                rc = pose_soa6(c->stream, d_soa6, (float*)sl.buf.p, n, *pose, c->err);
+            } else if (d_soa6) {
                 if (hipMemcpyAsync(sl.buf.p, d_soa6, n * 24, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
                     rc = fail(c, IMLS_ERR_DEVICE, "map slot copy");
             } else {
                 rc = upload_soa6(c, sl.buf, xyz, nrm, n, stride, 0);
+                if (!rc && pose && !inc) rc = pose_soa6(c->stream, (const float*)sl.buf.p, (float*)sl.buf.p, n, *pose, c->err);
             }
             raw = (const float*)sl.buf.p;
         }
         // incremental: this scan's NaN filter now, on the stream (its kept count into the pinned word
         // of its run id); its run is sorted at the next build
         if (!rc && inc && (rc = ensure_fifo(c)) == IMLS_OK)
-            rc = filter_async(c->stream, raw, n, sl.fpt, sl.fnr, c->tscratch, nullptr, &c->h_fifo_cnt[sl.id], c->err);
+            rc = filter_async(c->stream, raw, n, sl.fpt, sl.fnr, c->tscratch, nullptr, &c->h_fifo_cnt[sl.id], c->err, pose);
         if (rc) { c->slot_pool.push_back(sl); return rc; }
     }
     c->fifo.push_back(sl);
@@ -1722,29 +1767,81 @@ static int map_push(imls_ctx* c, const float* xyz, const float* nrm, size_t n, s
         c->fifo.pop_front();
     }
     if (inc) return fifo_set_target(c, n_map);
-    for (const auto& e : c->fifo)     // a scan indexed in place (max_queue_size was 1) is not held
-        if (e.ghost && e.n > 0) return fail(c, IMLS_ERR_STATE, "map FIFO holds a scan pushed with max_queue_size 1 (not kept): push again");
-    const size_t M = c->map_points;
-    if (M == 0) {                     // empty map (max_queue_size 0 or empty scans): no target
-        c->tgt_pending = false;
-        c->has_target = false;
-        c->has_corr = false;
-        c->M = 0;
-        if (n_map) *n_map = 0;
+    return map_assemble(c, n_map);
+}
+
+// a caller's pose: every entry finite; *identity when it is exactly I (then the plain path runs:
+// the same bits by construction, signed zeros included)
+static bool read_pose(const double pose[16], Pose12* out, bool* identity) {
+    bool id = true;
+    for (int k = 0; k < 16; ++k) {
+        if (!std::isfinite(pose[k])) return false;
+        if (pose[k] != ((k % 5 == 0) ? 1.0 : 0.0)) id = false;
+        if (k < 12) out->T[k] = pose[k];
+    }
+    *identity = id;
+    return true;
+}
+
+int imls_set_initial_pose(imls_ctx* c, const double pose[16]) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!pose) {
+        for (int k = 0; k < 16; ++k) c->init_pose[k] = (k % 5 == 0) ? 1.0 : 0.0;
         return IMLS_OK;
     }
-    for (const auto& e : c->fifo)     // one non-empty entry (max_queue_size 1): index it in place
-        if (e.n == M) return do_set_target(c, (const float*)e.buf.p, M, n_map);
-    if (!grow(c->macc, M * 24)) return fail(c, IMLS_ERR_DEVICE, "hipMalloc (map)");
-    size_t off = 0;
-    for (const auto& e : c->fifo) {
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(pose[k])) return fail(c, IMLS_ERR_ARG, "initial pose: non-finite entry");
+    std::memcpy(c->init_pose, pose, sizeof(c->init_pose));
+    return IMLS_OK;
+}
+
+int imls_map_push_posed(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, const double pose[16],
+                        size_t* n_map) {
+    if (!c) return IMLS_ERR_ARG;
+    if (n > 0 && (!xyz || !nrm || stride < 3)) return fail(c, IMLS_ERR_ARG, "bad cloud pointer/stride");
+    Pose12 P;
+    bool identity = false;
+    if (!pose || !read_pose(pose, &P, &identity)) return fail(c, IMLS_ERR_ARG, "map pose: null or non-finite entry");
+    if (int rc = check_device(c)) return rc;
+    return map_push(c, xyz, nrm, n, stride, nullptr, n_map, identity ? nullptr : &P);
+}
+
+int imls_map_push_posed_device(imls_ctx* c, const float* d_soa6, size_t n, const double pose[16], size_t* n_map) {
+    if (!c || (n > 0 && !d_soa6)) return IMLS_ERR_ARG;
+    Pose12 P;
+    bool identity = false;
+    if (!pose || !read_pose(pose, &P, &identity)) return fail(c, IMLS_ERR_ARG, "map pose: null or non-finite entry");
+    if (int rc = check_device(c)) return rc;
+    return map_push(c, nullptr, nullptr, n, 0, d_soa6, n_map, identity ? nullptr : &P);
+}
+
+// Every FIFO entry re-expressed in a new map frame (pose = new ← old), elementwise on the arrays the
+// entries keep (the incremental index: each scan's filtered records; else its raw SoA6 scan); the
+// quantisation frame is dropped, so the next build re-keys every run (fifo_build, !fq_valid).
+int imls_map_rebase(imls_ctx* c, const double pose[16]) {
+    if (!c) return IMLS_ERR_ARG;
+    Pose12 P;
+    bool identity = false;
+    if (!pose || !read_pose(pose, &P, &identity)) return fail(c, IMLS_ERR_ARG, "map pose: null or non-finite entry");
+    if (c->pending || c->batch_member) return fail(c, IMLS_ERR_STATE, "a registration is pending: collect its result first");
+    if (int rc = check_device(c)) return rc;
+    if (identity || c->map_points == 0) return IMLS_OK;
+    for (const auto& e : c->fifo)
+        if (e.ghost && e.n > 0)
+            return fail(c, IMLS_ERR_STATE, "map FIFO holds a scan indexed in place (max_queue_size 1, not kept): nothing to rebase");
+    const bool inc = fifo_incremental(c);
+    for (auto& e : c->fifo) {
         if (e.n == 0) continue;
-        if (hipMemcpy2DAsync((float*)c->macc.p + off, M * 4, e.buf.p, e.n * 4, e.n * 4, 6, hipMemcpyDeviceToDevice,
-                             c->stream) != hipSuccess)
-            return fail(c, IMLS_ERR_DEVICE, "map assembly copy");
-        off += e.n;
+        // (a filter whose count has not been read yet kept at most e.n records: the arrays hold e.n)
+        const int rc = inc ? pose_records(c->stream, (float4*)e.fpt.p, (float4*)e.fnr.p, e.nk >= 0 ? (size_t)e.nk : e.n, P, c->err)
+                           : pose_soa6(c->stream, (const float*)e.buf.p, (float*)e.buf.p, e.n, P, c->err);
+        if (rc) return rc;
     }
-    return do_set_target(c, (const float*)c->macc.p, M, n_map);
+    if (!inc) return map_assemble(c, nullptr);
+    c->fq_valid = false;
+    c->merged_ids.clear();
+    c->m_n = 0;
+    return fifo_set_target(c, nullptr);
 }
 
 int imls_map_push(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, size_t* n_map) {
@@ -1967,7 +2064,7 @@ int imls_register_frame_async(imls_ctx* c) {
     const int trace_words = std::max(iters, 1) * (int)(sizeof(imls_iter_trace) / 8);
     k_frame_init<<<1, 256, 0, c->stream>>>(c->st.pose, c->st.done, c->st.status, c->st.iters,
                                            (unsigned long long*)c->trace_mem.p, trace_words,
-                                           (unsigned long long*)c->stats.p);
+                                           (unsigned long long*)c->stats.p, init_pose_of(c));
     imls_iter_trace* tr = (imls_iter_trace*)c->trace_mem.p;
     if (int rc = ensure_map_normals(c)) return rc;
     const TreeView tv = tree_view(c);
@@ -2045,13 +2142,17 @@ int imls_register_frame(imls_ctx* c, double pose_out[16], int* iters_run, int* s
 namespace {
 
 constexpr int kResStride = 20;   // per frame: pose[16], iters, status
+// the batch's frame table is followed by every frame's initial pose ([n] records, then [n][16] doubles)
+static_assert(sizeof(PairDev) % alignof(double) == 0, "initial poses follow the frame table");
+constexpr size_t kTabEntryBytes = sizeof(PairDev) + 16 * sizeof(double);
 
-// rPose = I, done / status / iters = 0, the frame's trace and counters cleared (one launch for the
-// whole batch instead of six fills per frame)
-__global__ void k_batch_init(const PairDev* __restrict__ tab, int iters) {
+// rPose = the frame's initial pose (init[16·frame]; identity unless imls_set_initial_pose), done /
+// status / iters = 0, the frame's trace and counters cleared (one launch for the whole batch
+// instead of six fills per frame)
+__global__ void k_batch_init(const PairDev* __restrict__ tab, int iters, const double* __restrict__ init) {
     const PairDev A = tab[blockIdx.x];
     const int t = threadIdx.x;
-    if (t < 16) A.st.pose[t] = (t % 5 == 0) ? 1.0 : 0.0;
+    if (t < 16) A.st.pose[t] = init[(size_t)blockIdx.x * 16 + t];
     if (t == 0) { *A.st.done = 0; *A.st.status = 0; *A.st.iters = 0; }
     if (A.stats && t < 16) A.stats[t] = 0ull;
     unsigned long long* tr = reinterpret_cast<unsigned long long*>(A.trace);
@@ -2173,7 +2274,7 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         if (L->tab_h) (void)hipHostFree(L->tab_h);
         L->tab_h = nullptr;
         L->tab_cap = 0;
-        if (hipHostMalloc((void**)&L->tab_h, n * sizeof(PairDev)) != hipSuccess)
+        if (hipHostMalloc((void**)&L->tab_h, n * kTabEntryBytes) != hipSuccess)
             return fail(L, IMLS_ERR_DEVICE, "hipHostMalloc (batch)");
         L->tab_cap = (int)n;
     }
@@ -2184,7 +2285,7 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         if (hipHostMalloc((void**)&L->res_h, res_bytes) != hipSuccess) return fail(L, IMLS_ERR_DEVICE, "hipHostMalloc (batch)");
         L->res_h_bytes = res_bytes;
     }
-    if (!grow(L->tab_d, n * sizeof(PairDev)) || !grow(L->res_d, res_bytes))
+    if (!grow(L->tab_d, n * kTabEntryBytes) || !grow(L->res_d, res_bytes))
         return fail(L, IMLS_ERR_DEVICE, "hipMalloc (batch)");
     if (!L->ev_batch && hipEventCreateWithFlags(&L->ev_batch, hipEventDisableTiming) != hipSuccess)
         return fail(L, IMLS_ERR_DEVICE, "hipEventCreate (batch)");
@@ -2212,6 +2313,7 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         if (int rc = check_tv_ready(c)) return fail(L, rc, "context " + std::to_string(k) + ": " + c->err);
         if (int rc = prepare_ransac(c, c->N)) return fail(L, rc, c->err);
         L->tab_h[k] = pair_dev(c);
+        std::memcpy(reinterpret_cast<double*>(L->tab_h + n) + 16 * k, c->init_pose, 16 * sizeof(double));
         L->tab_h[k].recompute_normals = need_nrm ? 1 : 0;
         L->member_n[k] = c->N;
         if (c != L && hipStreamQuery(c->stream) != hipSuccess) {
@@ -2226,8 +2328,8 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
     (void)hipSetDevice(L->device);
     hs.mark("members");
     const PairDev* tab = (const PairDev*)L->tab_d.p;
-    hipMemcpyAsync(L->tab_d.p, L->tab_h, n * sizeof(PairDev), hipMemcpyHostToDevice, s);
-    k_batch_init<<<(unsigned)n, 64, 0, s>>>(tab, iters);
+    hipMemcpyAsync(L->tab_d.p, L->tab_h, n * kTabEntryBytes, hipMemcpyHostToDevice, s);
+    k_batch_init<<<(unsigned)n, 64, 0, s>>>(tab, iters, reinterpret_cast<const double*>(tab + n));
     if (any_nrm && launch_map_normals_batch(s, tab, (int)n, max_m, L->P.search_number_normal, L->P.r_normal))
         return fail(L, IMLS_ERR_DEVICE, "batched map normal launch failed");
     const KParams kp = L->kp;

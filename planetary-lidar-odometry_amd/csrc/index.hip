@@ -52,6 +52,75 @@ __global__ void k_compact(const float* __restrict__ soa, size_t n, const unsigne
     if (kept_index) kept_index[o] = (unsigned)i;
 }
 
+// float(P·[p;1]) and float(R·n) in transform_query's arithmetic (geom.h): double products summed in
+// order, no contraction (the build's -ffp-contract=off), one rounding to float per component.
+__device__ __forceinline__ void pose_point(const Pose12& P, float x, float y, float z, float nx, float ny, float nz,
+                                           float o[3], float on[3]) {
+    const double pd[3] = {x, y, z}, nd[3] = {nx, ny, nz};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double v = P.T[r * 4 + 0] * pd[0];
+        v = v + P.T[r * 4 + 1] * pd[1];
+        v = v + P.T[r * 4 + 2] * pd[2];
+        v = v + P.T[r * 4 + 3] * 1.0;
+        o[r] = (float)v;
+        double w = P.T[r * 4 + 0] * nd[0];
+        w = w + P.T[r * 4 + 1] * nd[1];
+        w = w + P.T[r * 4 + 2] * nd[2];
+        on[r] = (float)w;
+    }
+}
+
+// k_compact for a posed map push: the same scatter, each kept point written in the map frame.  The
+// pose is a launch argument (constant address space: scalar loads, wave-uniform).
+__global__ void k_compact_posed(const float* __restrict__ soa, size_t n, const unsigned* __restrict__ flag,
+                                const unsigned* __restrict__ pos, float4* __restrict__ pt, float4* __restrict__ nr,
+                                unsigned* __restrict__ kept_index, int* __restrict__ count, int* __restrict__ h_count,
+                                const Pose12 P) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == n - 1) {
+        const int c = (int)(pos[i] + flag[i]);
+        *count = c;
+        *h_count = c;
+    }
+    if (!flag[i]) return;
+    unsigned o = pos[i];
+    float x[3], nn[3];
+    pose_point(P, soa[i], soa[n + i], soa[2 * n + i], soa[3 * n + i], soa[4 * n + i], soa[5 * n + i], x, nn);
+    pt[o] = make_float4(x[0], x[1], x[2], 0.f);
+    nr[o] = make_float4(nn[0], nn[1], nn[2], 0.f);
+    if (kept_index) kept_index[o] = (unsigned)i;
+}
+
+// an SoA6 scan re-expressed under P (out may be in: every thread reads its point before it writes it)
+__global__ void k_pose_soa6(const float* in, float* out, size_t n, const Pose12 P) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = in[k * n + i];
+    if (isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2])) {
+        float x[3], nn[3];
+        pose_point(P, v[0], v[1], v[2], v[3], v[4], v[5], x, nn);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { v[k] = x[k]; v[3 + k] = nn[k]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[k * n + i] = v[k];
+}
+
+// filtered float4 records re-expressed under P in place (imls_map_rebase): 16-B loads and stores
+__global__ void k_pose_records(float4* __restrict__ pt, float4* __restrict__ nr, size_t n, const Pose12 P) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pt[i], q = nr[i];
+    float x[3], nn[3];
+    pose_point(P, p.x, p.y, p.z, q.x, q.y, q.z, x, nn);
+    pt[i] = make_float4(x[0], x[1], x[2], p.w);
+    nr[i] = make_float4(nn[0], nn[1], nn[2], q.w);
+}
+
 __global__ void k_bbox_partial(const float4* __restrict__ pt, int M, float* __restrict__ part) {
     __shared__ float red[6][kBlock];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -190,7 +259,7 @@ inline unsigned grid_for(size_t n, int b = kBlock) { return (unsigned)((n + b - 
 // NaN filter + order-keeping compaction, asynchronous: the kept count lands in *h_count (pinned,
 // device-visible host memory) from the compaction kernel itself — valid once the stream has passed it.
 int filter_async(hipStream_t s, const float* d_soa6, size_t n_in, DevBuf& pt, DevBuf& nr, DevBuf& scratch,
-                 unsigned* d_kept, int* h_count, std::string& err) {
+                 unsigned* d_kept, int* h_count, std::string& err, const Pose12* pose) {
     size_t cub_bytes = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, cub_bytes, (unsigned*)nullptr, (unsigned*)nullptr, (int)n_in, s) != hipSuccess) {
         err = "hipcub scan size query failed";
@@ -205,9 +274,33 @@ int filter_async(hipStream_t s, const float* d_soa6, size_t n_in, DevBuf& pt, De
     void* cub_tmp = carve<char>(p, cub_bytes);
     k_flag_finite<<<grid_for(n_in), kBlock, 0, s>>>(d_soa6, n_in, flag);
     hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, flag, pos, (int)n_in, s);
-    k_compact<<<grid_for(n_in), kBlock, 0, s>>>(d_soa6, n_in, flag, pos, (float4*)pt.p, (float4*)nr.p, d_kept, cnt, h_count);
+    if (pose)
+        k_compact_posed<<<grid_for(n_in), kBlock, 0, s>>>(d_soa6, n_in, flag, pos, (float4*)pt.p, (float4*)nr.p, d_kept, cnt,
+                                                          h_count, *pose);
+    else
+        k_compact<<<grid_for(n_in), kBlock, 0, s>>>(d_soa6, n_in, flag, pos, (float4*)pt.p, (float4*)nr.p, d_kept, cnt, h_count);
     if (hipGetLastError() != hipSuccess) {
         err = "filter/compact launch failed";
+        return IMLS_ERR_DEVICE;
+    }
+    return IMLS_OK;
+}
+
+int pose_soa6(hipStream_t s, const float* in, float* out, size_t n, const Pose12& pose, std::string& err) {
+    if (n == 0) return IMLS_OK;
+    k_pose_soa6<<<grid_for(n), kBlock, 0, s>>>(in, out, n, pose);
+    if (hipGetLastError() != hipSuccess) {
+        err = "pose launch failed";
+        return IMLS_ERR_DEVICE;
+    }
+    return IMLS_OK;
+}
+
+int pose_records(hipStream_t s, float4* pt, float4* nr, size_t n, const Pose12& pose, std::string& err) {
+    if (n == 0) return IMLS_OK;
+    k_pose_records<<<grid_for(n), kBlock, 0, s>>>(pt, nr, n, pose);
+    if (hipGetLastError() != hipSuccess) {
+        err = "pose launch failed";
         return IMLS_ERR_DEVICE;
     }
     return IMLS_OK;

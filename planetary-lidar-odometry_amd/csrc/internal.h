@@ -290,8 +290,17 @@ __device__ __forceinline__ PairDev device_view(const PairDev* pa) {
 //     the kept count copied to pinned *h_count behind it;
 // (B) with that count known: build_target_tree (Morton sort, leaf boxes, node records) or
 //     source_order (the source's Morton order = the wave kernels' query order).
+// A rigid pose (rows 0-2 of the row-major 4×4) handed to a kernel by value: launch arguments live in
+// the constant address space, so a wave reads it with one set of scalar loads (as transform_query's).
+struct Pose12 { double T[12]; };
+// `pose` (nullable): the posed map push — a kept point leaves the scatter pass as float(pose·[p;1])
+// and its normal rotated, in transform_query's arithmetic (geom.h); the filter tests the point as given.
 int filter_async(hipStream_t s, const float* d_soa6, size_t n_in, DevBuf& pt, DevBuf& nr, DevBuf& scratch,
-                 unsigned* d_kept, int* h_count, std::string& err);
+                 unsigned* d_kept, int* h_count, std::string& err, const Pose12* pose = nullptr);
+// The same arithmetic elementwise: an SoA6 scan [6][n] into `out` (may be `in`; a point with a
+// non-finite coordinate is copied as given), and filtered float4 records in place (w kept).
+int pose_soa6(hipStream_t s, const float* in, float* out, size_t n, const Pose12& pose, std::string& err);
+int pose_records(hipStream_t s, float4* pt, float4* nr, size_t n, const Pose12& pose, std::string& err);
 // (A) for many frames at once (deferred filters of a batch's members), one launch sequence; the
 // kept counts land in each job's pinned host word once the stream has passed it.
 struct FilterJob {

@@ -48,6 +48,13 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _pose16(pose) -> np.ndarray:
+    p = np.ascontiguousarray(pose, dtype=np.float64)
+    if p.size != 16:
+        raise ValueError("a pose is 4×4 (row-major)")
+    return p.reshape(16)
+
+
 _XYZ_OFF = POINT_DTYPE.fields["x"][1]
 _NRM_OFF = POINT_DTYPE.fields["normal_x"][1]
 
@@ -164,25 +171,43 @@ class ImlsContext:
         return self.n_source
 
     # -- map FIFO (accumulateTargetCloud, laser_odometry.cpp:116-136) ---------------------------
-    def map_push(self, cloud, count: bool = True):
+    def map_push(self, cloud, count: bool = True, pose=None):
         """accumulateTargetCloud(cloud, max_queue_size) + setTargetPointCloud(accumulatedTargetCloud):
         the scan joins the device-resident FIFO (only it crosses PCIe) and the index is rebuilt over
-        the FIFO's scans, oldest first.  Returns the map size after the NaN filter (count=True)."""
+        the FIFO's scans, oldest first.  Returns the map size after the NaN filter (count=True).
+        pose (4×4, map ← scan; None = the plain push): the scan enters the FIFO expressed in the map
+        frame (imls_map_push_posed)."""
         _keep, px, pn, m, stride = _cloud_args(cloud)
         n = C.c_size_t()
         np_ = C.byref(n) if count else None
         if m == 0:
-            self._check(self.lib.imls_map_push(self.ctx, None, None, 0, 6, np_))
-        else:
+            px, pn, stride = None, None, 6
+        if pose is None:
             self._check(self.lib.imls_map_push(self.ctx, px, pn, m, stride, np_))
+        else:
+            self._check(self.lib.imls_map_push_posed(self.ctx, px, pn, m, stride, _ptr(_pose16(pose)), np_))
         self.n_target = n.value if count else None
         return self.n_target
 
-    def map_push_device(self, soa6_ptr: int, n: int, count: bool = True):
+    def map_push_device(self, soa6_ptr: int, n: int, count: bool = True, pose=None):
         k = C.c_size_t()
-        self._check(self.lib.imls_map_push_device(self.ctx, C.c_void_p(soa6_ptr), n, C.byref(k) if count else None))
+        kp = C.byref(k) if count else None
+        if pose is None:
+            self._check(self.lib.imls_map_push_device(self.ctx, C.c_void_p(soa6_ptr), n, kp))
+        else:
+            self._check(self.lib.imls_map_push_posed_device(self.ctx, C.c_void_p(soa6_ptr), n, _ptr(_pose16(pose)), kp))
         self.n_target = k.value if count else None
         return self.n_target
+
+    def map_rebase(self, pose):
+        """Every FIFO entry re-expressed in a new map frame (pose = new ← old, imls_map_rebase); the
+        index is rebuilt at its next use."""
+        self._check(self.lib.imls_map_rebase(self.ctx, _ptr(_pose16(pose))))
+
+    def set_initial_pose(self, pose=None):
+        """rPose at the start of every later registration of this context (imls_set_initial_pose);
+        None restores identity."""
+        self._check(self.lib.imls_set_initial_pose(self.ctx, None if pose is None else _ptr(_pose16(pose))))
 
     def map_clear(self):
         self._check(self.lib.imls_map_clear(self.ctx))
@@ -699,16 +724,51 @@ def chain_pose(prev, rel) -> np.ndarray:
                       for j in range(4)] for i in range(4)])
 
 
+def inv_pose(T) -> np.ndarray:
+    """The closed-form inverse [Rᵀ | −Rᵀt] of a rigid 4×4 pose, in double."""
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    R, t = T[:3, :3], T[:3, 3]
+    out = np.eye(4)
+    out[:3, :3] = R.T
+    for i in range(3):
+        out[i, 3] = -((R[0, i] * t[0] + R[1, i] * t[1]) + R[2, i] * t[2])
+    return out
+
+
 class LaserOdometry:
     """processData (laser_odometry.cpp:416-683) minus ROS: per (filteredLaserCloud, flatCloud)
     frame, the first frame only seeds the map (Q13); every later frame registers its flat cloud
     against the map FIFO (rPose = I, the fused device loop), chains nowPose = prevLaserPose·rPose
     and appends it to `pose_file` (savePoseToFile, 659); then the filtered cloud joins the FIFO
     (accumulateTargetCloud, 663-664).  The FIFO lives in HBM (ImlsContext.map_push): only the new
-    scan crosses PCIe each frame.  The context (and its RANSAC rand() stream) persists across frames."""
+    scan crosses PCIe each frame.  The context (and its RANSAC rand() stream) persists across frames.
+
+    map_model "raw" (default) is the reference's FIFO: every scan stays in its own sensor frame, so a
+    queue of several scans is a smeared map.  "compensated" keeps the FIFO in one fixed map frame
+    (scan-to-model): the driver carries T_A, the previous scan's pose in that frame (I at the first
+    push); frame k starts its registration at T_A (ImlsContext.set_initial_pose), the result is its
+    own pose T_A' in the map frame, rPose = inv(T_A)·T_A' (what is chained, written and reported, as
+    before), and its filtered scan is pushed with pose T_A' (map_push(pose=…)).  Once ‖t(T_A')‖ exceeds
+    rebase_distance the map is re-expressed in the newest scan's frame (map_rebase(inv(T_A')), T_A =
+    I) so float map coordinates stay near the sensor.  A frame that does not register keeps T_A and
+    reports rPose = I.  With max_queue_size 1 the anchor is always the newest scan (pushed as it is,
+    the pipelined path kept).  motion_prior "constant_velocity" starts frame k at T_A·(last rPose)
+    instead of T_A (either map model).  In "compensated" mode the trace's poses (and the
+    imls_iter_results.txt of output_dir) are poses in the map frame."""
 
     def __init__(self, params: Optional[_abi.ImlsParams] = None, device: int = 0, pose_file: Optional[str] = None,
-                 output_dir: Optional[str] = None, pipelined: Optional[bool] = None):
+                 output_dir: Optional[str] = None, pipelined: Optional[bool] = None, map_model: str = "raw",
+                 motion_prior: str = "none", rebase_distance: float = 100.0):
+        if map_model not in ("raw", "compensated"):
+            raise ValueError('map_model: "raw" or "compensated"')
+        if motion_prior not in ("none", "constant_velocity"):
+            raise ValueError('motion_prior: "none" or "constant_velocity"')
+        self.map_model = map_model
+        self.motion_prior = motion_prior
+        self.rebase_distance = float(rebase_distance)
+        self.anchor_pose = np.eye(4)    # T_A: the previous scan in the map frame ("compensated", queue > 1)
+        self.last_rpose = np.eye(4)     # the last frame's rPose (the constant-velocity first guess)
+        self.rebases = 0
         self.ctx = ImlsContext(params, device)
         # pipelined (default for max_queue_size 1, the shipped config): two contexts alternate.  Frame
         # k registers on the one holding scan k−1's index while its own filtered scan goes to the
@@ -775,6 +835,11 @@ class LaserOdometry:
         nxt = self._ctxs[1 - self._cur] if self.pipelined else ctx   # where this frame's scan goes
         pushed = False
         registers = self.frame_count != 0 and n_flat != 0 and ctx.n_target != 0
+        # scan-to-model: the map lives in a fixed frame, this frame starts at its predicted pose in it
+        posed = self.map_model == "compensated" and ctx.params.max_queue_size > 1
+        predicted = self.motion_prior == "constant_velocity"
+        if registers and (posed or predicted):
+            ctx.set_initial_pose(chain_pose(self.anchor_pose, self.last_rpose) if predicted else self.anchor_pose)
         if registers:
             # the flat cloud's upload: this path's preprocessing.  Count-less: the registration waits
             # for the filter's count itself, so the host does not also wait here for the count and the
@@ -799,6 +864,12 @@ class LaserOdometry:
                 result = ctx.register_frame()
             if registers and self.output_dir:
                 self._save_iterations(result, timestamp)
+            if registers and posed:
+                # the registration gave this scan's pose in the map frame: rPose = inv(T_A)·T_A'
+                result["map_pose"] = result["pose"]
+                result["pose"] = chain_pose(inv_pose(self.anchor_pose), result["map_pose"])
+                self.anchor_pose = result["map_pose"]
+            self.last_rpose = result["pose"]
             now = chain_pose(self.prev_pose, result["pose"])
             self.prev_pose = now
             self.poses.append((timestamp, now))
@@ -808,7 +879,11 @@ class LaserOdometry:
             if times:
                 times.step("2. Matching and solving in flat points")
         if not pushed:
-            nxt.map_push(filtered_cloud)
+            nxt.map_push(filtered_cloud, pose=self.anchor_pose if posed else None)
+            if posed and float(np.linalg.norm(self.anchor_pose[:3, 3])) > self.rebase_distance:
+                nxt.map_rebase(inv_pose(self.anchor_pose))
+                self.anchor_pose = np.eye(4)
+                self.rebases += 1
         if nxt is not ctx:
             if ctx.params.solve_method == _abi.IMLS_SOLVE_RANSAC:
                 nxt.set_rng_state(ctx.rng_state())      # one rand() stream across the frames
