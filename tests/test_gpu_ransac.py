@@ -14,6 +14,7 @@ import pytest
 
 import oracle_ctypes as oc
 from planetary_lidar_odometry_amd import _abi, config, imls_icp
+from ransac_cases import outlier_set      # shared with test_gpu_ransac_sizes.py (same rows as ever)
 
 pytestmark = pytest.mark.gpu
 GOLDEN = pathlib.Path(__file__).resolve().parent / "golden"
@@ -44,22 +45,6 @@ def ctx():
     c = imls_icp.ImlsContext(shipped_params())
     yield c
     c.close()
-
-
-def outlier_set(n=4000, frac=0.3, seed=7):
-    """Correspondences of a known motion on three plane families, `frac` of them corrupted."""
-    rng = np.random.default_rng(seed)
-    s = rng.uniform(-15, 15, (n, 3))
-    nrm = np.zeros((n, 3))
-    nrm[np.arange(n), rng.integers(0, 3, n)] = 1.0
-    nrm += rng.normal(0, 0.05, (n, 3))
-    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    a = 0.02
-    R = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
-    d = s @ R.T + np.array([0.3, -0.1, 0.05])
-    bad = rng.random(n) < frac
-    d[bad] += rng.normal(0, 2.0, (bad.sum(), 3))
-    return s, d, nrm
 
 
 @pytest.mark.parametrize("final", ["LS", "WLS", "DRPM"])
