@@ -494,6 +494,67 @@ int imls_sample_point_cloud(imls_ctx* ctx, const imls_sample_params* p, const fl
                             const float* last_xyz, size_t last_stride_floats, size_t m, int32_t* sampled_out,
                             size_t* n_sampled, float* bin_weights_out);
 
+/* scan_registration.presample_method.curvature (config.json; read at scan_registration.cpp:1073, 1464).
+ * imls_default_curvature_params() fills the shipped values. */
+typedef struct imls_curvature_params {
+    int32_t window_size;            /* curvature.window_size = 5 */
+    float curvature_threshold;      /* curvature.curvature_threshold = 0.02 */
+} imls_curvature_params;
+void imls_default_curvature_params(imls_curvature_params* p);
+
+/* Replaces the "curvature" presample: the per-point curvature by difference (scan_registration.cpp:
+ * 1071-1113), the threshold (1462-1473) and the invalid-index erase (1481-1489).
+ *   xyz / ring_sizes[n_rings]: laserCloud, exactly as imls_ring_normals_pca takes it (N = Σ ring sizes);
+ *   row_index / row_flags [n_rows]: that call's index_out / flags_out (the rows of filteredLaserCloud).
+ * With w = window_size: ring i with prefix off_i visits the global indices j in [off_i + 5,
+ * off_i + size_i − 6) (1076; empty for rings under 12 points); a visited j with j >= w && j < N − w
+ * (1081) gets, from three float sums d += p[j+k] − p[j] over k = −w … w in that order at GLOBAL
+ * indices (the window runs across ring boundaries), curvature = (dx·dx + dy·dy) + dz·dz in float,
+ * no contraction; a visited j failing the test gets 0 (1109).  Every point the loop does not visit
+ * keeps 0 — unpinned: that is pcl::PointXYZINormal's default constructor as inferred from PCL's
+ * sources, not a value this project's oracle measured.
+ *   curvature_out (nullable, N floats): the per-point curvature;
+ *   candidates_out (capacity n_rows) / *n_cand: the rows r, ascending, with
+ *     curvature[row_index[r]] > curvature_threshold (float compare, strict; 1467) and without
+ *     IMLS_PCA_PLANE_INVALID (the erase at 1481-1489; such rows exist only under use_all_points).
+ * filteredLaserCloud's curvature field is curvature_out[row_index[r]] (1220).  window_size < 0, a
+ * row index >= N → IMLS_ERR_ARG.  Requires n_rings ≤ 4096 and ring sizes ≤ 1<<20. */
+int imls_presample_curvature(imls_ctx* ctx, const imls_curvature_params* p, const float* xyz, size_t stride_floats,
+                             const int32_t* ring_sizes, int32_t n_rings, const uint32_t* row_index,
+                             const uint8_t* row_flags, size_t n_rows, float* curvature_out, int32_t* candidates_out,
+                             size_t* n_cand);
+
+/* Replaces samplePointCloud "three_axis" (scan_registration.cpp:769-773 → threeAxisSampling 492-533).
+ *   xyz/nrm: pcl_cloud, point i at xyz + i*stride_floats (nrm likewise), n points;
+ *   evals[3n]: eigenvalues_matrix columns (λ1, λ2, λ3) = evals_out of imls_ring_normals_pca;
+ *   candidates[n_cand]: candidate_indices, DISTINCT indices into the cloud (as every presample
+ *     produces them; with a repeated index the order of its copies in a list is unspecified).
+ * Per candidate idx: aD = float((sqrt((double)λ2) − sqrt((double)λ3)) / sqrt((double)λ1)) (506: the
+ * unqualified sqrt takes the double overload), a2D = aD·aD in float, c = p × n in float without
+ * FMA, and nine values in list order: a2D·c.x, (−a2D)·c.x, a2D·c.y, (−a2D)·c.y, a2D·c.z, (−a2D)·c.z,
+ * a2D·|n.x|, a2D·|n.y|, a2D·|n.z| (511-519; the dot products with the unit axes are evaluated
+ * literally, so a non-finite component gives the reference's NaN).  Each list is ordered by
+ * std::greater<std::pair<float, int>> (525): larger value first, equal values (+0 and −0 are equal)
+ * → larger idx first.  sampled_out (capacity 9·min(points_per_list, n_cand)) receives list 0's first
+ * min(points_per_list, n_cand) indices, then list 1's, …; a point heading several lists appears
+ * several times (523).  *n_sampled = 9·min(points_per_list, n_cand).
+ * Deliberate definition: a NaN value makes the reference's std::sort undefined behaviour; here
+ * NaN-valued entries rank after every other entry of their list, by descending idx, and
+ * *nan_keys (nullable) counts them over the nine lists (0 on every valid configuration: λ of the
+ * candidates are positive).
+ * points_per_list (shipped 200) must be in [1, 4096], else IMLS_ERR_UNSUPPORTED. */
+int imls_sample_three_axis(imls_ctx* ctx, int32_t points_per_list, const float* xyz, const float* nrm,
+                           size_t stride_floats, size_t n, const float* evals, const int32_t* candidates,
+                           size_t n_cand, int32_t* sampled_out, size_t* n_sampled, uint64_t* nan_keys);
+
+/* Replaces samplePointCloud "random" (scan_registration.cpp:779-781 → randomSampling 566-582): the
+ * candidates shuffled by std::shuffle with std::mt19937(shuffle_seed), the first
+ * min(max_points, n_cand) entries (max_points: shipped 2000; < 0 → IMLS_ERR_ARG).  Host only.  The
+ * reference seeds the generator from std::random_device (571-572: not reproducible), hence the
+ * explicit seed, as imls_sample_params.shuffle_seed.  sampled_out: capacity min(max_points, n_cand). */
+int imls_sample_random(imls_ctx* ctx, const int32_t* candidates, size_t n_cand, int32_t max_points,
+                       uint32_t shuffle_seed, int32_t* sampled_out, size_t* n_sampled);
+
 /* ---- nearest-neighbour queries ---------------------------------------------------------- */
 /* Replaces a Nabo::NNSearchD::knn call (imls_icp.cpp:197, 372, 414, 605, 650;
  * laser_odometry.cpp:348) with epsilon = 0 and SORT_RESULTS on the index the context already holds:
@@ -568,7 +629,9 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * 5 = k_ring_pca (imls_ring_normals_pca), 6 = k_major_avg (imls_sample_point_cloud, major_axis),
  * 7 = imls_scan_front_end (all its kernels), 8 = imls_knn / imls_knn_device (traversal, export and
  * exact fallback of each chunk; the queries' ordering is not included, as the source's is not in 0;
- * imls_knn_device's events are read by the next call that synchronises, e.g. imls_knn).  enable: 0 off, 1 every kind above (the members of
+ * imls_knn_device's events are read by the next call that synchronises, e.g. imls_knn),
+ * 9 = imls_sample_three_axis (keys and per-list top-k), 10 = imls_presample_curvature (stencil and
+ * candidate compaction).  enable: 0 off, 1 every kind above (the members of
  * an imls_register_frames batch then build their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */

@@ -161,6 +161,22 @@ def default_sample_params(method: int = IMLS_SAMPLE_MAJOR_AXIS) -> ImlsSamplePar
     return p
 
 
+class ImlsCurvatureParams(C.Structure):
+    """imls_curvature_params (include/imls_gpu.h): scan_registration.presample_method.curvature
+    (config.json, read at scan_registration.cpp:1073, 1464)."""
+    _fields_ = [("window_size", C.c_int32), ("curvature_threshold", C.c_float)]
+
+
+def default_curvature_params() -> ImlsCurvatureParams:
+    """The shipped config.json values (imls_default_curvature_params() in the library)."""
+    p = ImlsCurvatureParams()
+    p.window_size, p.curvature_threshold = 5, 0.02
+    return p
+
+
+THREE_AXIS_MAX_POINTS_PER_LIST = 4096   # imls_sample_three_axis: points_per_list in [1, 4096]
+
+
 class ImlsPairInput(C.Structure):
     """imls_pair_input (include/imls_gpu.h)."""
     _fields_ = [("src_xyz", C.c_void_p), ("src_nrm", C.c_void_p), ("n_src", C.c_size_t),
@@ -231,6 +247,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "imls_captured_correspondences": (C.c_int, [VP, C.c_int, SZ, VP, VP, VP, VP, P(SZ)]),
         "imls_timing_origin": (C.c_int, [VP]),
         "imls_timing_intervals": (C.c_int, [VP, C.c_int, VP, SZ, P(SZ)]),
+        "imls_default_curvature_params": (None, [P(ImlsCurvatureParams)]),
+        "imls_presample_curvature": (C.c_int, [VP, P(ImlsCurvatureParams), VP, SZ, VP, C.c_int32, VP, VP, SZ, VP, VP,
+                                               P(SZ)]),
+        "imls_sample_three_axis": (C.c_int, [VP, C.c_int32, VP, VP, SZ, SZ, VP, VP, SZ, VP, P(SZ), P(C.c_uint64)]),
+        "imls_sample_random": (C.c_int, [VP, VP, SZ, C.c_int32, C.c_uint32, VP, P(SZ)]),
         "imls_knn": (C.c_int, [VP, VP, SZ, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
         "imls_knn_device": (C.c_int, [VP, VP, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
     }
@@ -257,6 +278,7 @@ ABI_SYMBOLS = (
     "imls_timing_origin", "imls_timing_intervals", "imls_capture_correspondences",
     "imls_captured_correspondences", "imls_set_option", "imls_get_option", "imls_knn", "imls_knn_device",
     "imls_set_initial_pose", "imls_map_push_posed", "imls_map_push_posed_device", "imls_map_rebase",
+    "imls_default_curvature_params", "imls_presample_curvature", "imls_sample_three_axis", "imls_sample_random",
 )
 
 _LIB = None

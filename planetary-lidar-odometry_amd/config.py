@@ -5,6 +5,11 @@ laser_odometry.cpp reads at 487-518, 570, 606, 640-641 and the dispatcher 183-24
 key, ``laser_odometry.backend`` ("hip" — the only backend this package ships).  Method names are
 the reference's strings: matching "IMLS" / "plane_ICP"; solving "LS" / "RANSAC" / "Ceres" / "ICP" /
 "Teaser"; RANSAC final "LS" / "Weighted LS" / "DRPM".
+
+producer_from_config() reads the ``scan_registration`` section (scan_registration.cpp:771-799, 935,
+1073, 1132-1145, 1451, 1464, 1479) the same way: compute_normal_method "pca" on format
+"pointcloud"; presample_method "geometric_features" / "curvature"; sample_method "major_axis" /
+"normal" / "three_axis" / "random".
 """
 from __future__ import annotations
 
@@ -99,6 +104,106 @@ def params_from_config(cfg: dict) -> _abi.ImlsParams:
     if backend != "hip":
         raise ConfigError(f"laser_odometry.backend {backend!r}: only 'hip' is shipped")
     return p
+
+
+# scan_registration: the producer configurations the reference marks as verified run on the GPU; the
+# others it lists (its own results table marks them as not working) are refused by name.
+NORMAL_FORMATS = ("pointcloud",)
+NORMAL_METHODS = ("pca",)
+UNSUPPORTED_NORMAL_FORMATS = ("range_image",)
+UNSUPPORTED_NORMAL_METHODS = ("cross_product", "FALS", "SRI")
+PRESAMPLE = ("geometric_features", "curvature")
+UNSUPPORTED_PRESAMPLE = ("tensor_voting",)
+SAMPLE = ("major_axis", "normal", "three_axis", "random")
+NEIGHBOR_SCAN = {"kdtree": 0, "index": 1}
+SAMPLING_STRATEGY = {"FPS": _abi.SAMPLE_FPS, "random": _abi.SAMPLE_RANDOM}
+
+
+def _sample_block(block: dict, method: int) -> _abi.ImlsSampleParams:
+    sp = _abi.default_sample_params(method)
+    if "r" in block:
+        sp.r = float(block["r"])
+    if "r_proj" in block:
+        sp.r_proj = float(block["r_proj"])
+    if "max_total_points" in block:
+        sp.max_total_points = int(block["max_total_points"])
+    for key in ("azimuth_bins", "elevation_bins", "min_points_per_bin", "max_points_per_bin"):
+        if key in block:
+            setattr(sp, key, int(block[key]))
+    if "sampling_strategy" in block:
+        if block["sampling_strategy"] not in SAMPLING_STRATEGY:
+            raise ConfigError(f"Invalid sampling_strategy {block['sampling_strategy']!r}")
+        sp.sampling_strategy = SAMPLING_STRATEGY[block["sampling_strategy"]]
+    return sp
+
+
+def producer_from_config(cfg: dict, ctx=None, **kwargs):
+    """Build the GPU producer (producer.ScanRegistration) from the reference's scan_registration key
+    paths.  A key the file leaves out keeps its shipped value (a file without the section selects
+    the shipped pca → geometric_features → major_axis chain).  Methods outside the GPU path raise
+    ConfigError naming the method (the reference prints "Invalid …_METHOD!" and publishes empty
+    clouds; this fails once, at configuration time).  The context is created at the producer's
+    first use unless `ctx` is given, so a configuration can be validated without a GPU."""
+    from .producer import ScanRegistration
+
+    sr = cfg.get("scan_registration", {})
+    cn = sr.get("compute_normal_method", {})
+    fmt, method = cn.get("format", "pointcloud"), cn.get("method", "pca")
+    if fmt in UNSUPPORTED_NORMAL_FORMATS:
+        raise ConfigError(f"compute_normal_method.format {fmt!r} (FALS / SRI range images) is outside the GPU path")
+    if fmt not in NORMAL_FORMATS:
+        raise ConfigError(f"Invalid compute_normal_method.format {fmt!r}")
+    if method in UNSUPPORTED_NORMAL_METHODS:
+        raise ConfigError(f"compute_normal_method {method!r} is outside the GPU path (the reference marks it not working)")
+    if method not in NORMAL_METHODS:
+        raise ConfigError(f"Invalid COMPUTE_NORMAL_METHOD! {method!r}")
+    pca = _abi.default_pca_params()
+    pb = cn.get("pca", {})
+    if "window_size" in pb:
+        pca.window_size = int(pb["window_size"])
+    if "iter_step" in pb:
+        pca.iter_step = int(pb["iter_step"])
+    if "knn_distance_threshold" in pb:
+        pca.knn_distance_threshold = float(pb["knn_distance_threshold"])
+    if "neighbor_scan" in pb:
+        if pb["neighbor_scan"] not in NEIGHBOR_SCAN:
+            raise ConfigError(f"Invalid pca.neighbor_scan {pb['neighbor_scan']!r}")
+        pca.neighbor_scan = NEIGHBOR_SCAN[pb["neighbor_scan"]]
+    pc = pb.get("plane_constraint", {})
+    if "distance_threshold" in pc:
+        pca.distance_threshold = float(pc["distance_threshold"])
+    if "valid_points_threshold" in pc:
+        pca.valid_points_threshold = float(pc["valid_points_threshold"])
+    if "use_all_points" in sr.get("model", {}):
+        pca.use_all_points = int(bool(sr["model"]["use_all_points"]))
+    ps = sr.get("presample_method", {})
+    presample = ps.get("method", "geometric_features")
+    if presample in UNSUPPORTED_PRESAMPLE:
+        raise ConfigError(f"presample_method {presample!r} is outside the GPU path (the reference marks it not working)")
+    if presample not in PRESAMPLE:
+        raise ConfigError(f"Invalid PRESAMPLE_METHOD! {presample!r}")
+    if "planarity_threshold" in ps.get("geometric_features", {}):
+        pca.planarity_threshold = float(ps["geometric_features"]["planarity_threshold"])
+    curv = _abi.default_curvature_params()
+    cb = ps.get("curvature", {})
+    if "curvature_threshold" in cb:
+        curv.curvature_threshold = float(cb["curvature_threshold"])
+    if "window_size" in cb:
+        curv.window_size = int(cb["window_size"])
+    sm = sr.get("sample_method", {})
+    sample = sm.get("method", "major_axis")
+    if sample not in SAMPLE:
+        raise ConfigError(f"Invalid SAMPLE_METHOD! {sample!r}")
+    points_per_list = int(sm.get("three_axis", {}).get("points_per_list", 200))
+    if not 1 <= points_per_list <= _abi.THREE_AXIS_MAX_POINTS_PER_LIST:
+        raise ConfigError(f"three_axis.points_per_list {points_per_list}: the GPU path takes 1 … "
+                          f"{_abi.THREE_AXIS_MAX_POINTS_PER_LIST}")
+    return ScanRegistration(ctx=ctx, pca_params=pca, sample_method=sample, presample_method=presample,
+                            curvature_params=curv, points_per_list=points_per_list,
+                            max_points=int(sm.get("random", {}).get("max_points", 2000)),
+                            normal_params=_sample_block(sm.get("normal", {}), _abi.IMLS_SAMPLE_NORMAL),
+                            major_axis_params=_sample_block(sm.get("major_axis", {}), _abi.IMLS_SAMPLE_MAJOR_AXIS),
+                            **kwargs)
 
 
 def bench_params(iterations: int = 20) -> _abi.ImlsParams:

@@ -139,7 +139,8 @@ void release_retired(int device) {
 }
 }  // namespace imlsgpu
 
-constexpr int kTimingKinds = 9;   // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query
+constexpr int kTimingKinds = 11;  // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query,
+                                  // three_axis sampling, curvature presample
 
 // Runtime options of a context (imls_set_option; include/imls_gpu.h documents each): the validated
 // tuning parameters and test hooks.  Nothing is read from the environment.
@@ -220,6 +221,8 @@ struct imls_ctx {
     DevBuf pca_mem;                       // imls_ring_normals_pca scratch (upstream producer)
     DevBuf sample_mem;                    // imls_sample_point_cloud scratch
     DevBuf front_mem;                     // imls_scan_front_end scratch
+    DevBuf curv_mem;                      // imls_presample_curvature scratch
+    DevBuf ta_mem;                        // imls_sample_three_axis scratch
     // imls_knn / imls_knn_device: buffers of their own (one chunk of ≤ kKnnChunk queries), so a query
     // leaves the loaded source, its order, the correspondences and the neighbour lists alone —
     // queries (xyz, non-finite flag), their Morton order + the sort's scratch, the list block,
@@ -1288,7 +1291,7 @@ void imls_destroy(imls_ctx* c) {
     if (c->ustream) (void)hipStreamSynchronize(c->ustream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->knn_q, &c->knn_perm, &c->knn_scratch, &c->knn_lists, &c->knn_fb, &c->knn_pose, &c->knn_up, &c->knn_out,
-                      &c->cap_mem, &c->front_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
+                      &c->cap_mem, &c->front_mem, &c->curv_mem, &c->ta_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
                       &c->upload_t, &c->spt, &c->snr, &c->sscratch,
                       &c->upload_s, &c->cs, &c->cd, &c->cn, &c->solve_mem, &c->trace_mem, &c->stats, &c->rows_d, &c->pose_tmp};
     for (DevBuf* b : bufs)
@@ -2593,6 +2596,79 @@ int imls_sample_point_cloud(imls_ctx* c, const imls_sample_params* p, const floa
     if (mk && rc == IMLS_OK && p->method != IMLS_SAMPLE_MAJOR_AXIS) c->ev_pairs[6].pop_back();   // no kernel recorded
     if (c->timing) harvest_timing(c);
     return rc;
+}
+
+void imls_default_curvature_params(imls_curvature_params* p) {
+    // scan_registration.presample_method.curvature of the shipped config.json (read at 1073, 1464)
+    if (!p) return;
+    p->window_size = 5;
+    p->curvature_threshold = 0.02f;
+}
+
+int imls_presample_curvature(imls_ctx* c, const imls_curvature_params* p, const float* xyz, size_t stride,
+                             const int32_t* ring_sizes, int32_t n_rings, const uint32_t* row_index,
+                             const uint8_t* row_flags, size_t n_rows, float* curvature_out, int32_t* candidates_out,
+                             size_t* n_cand) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!p || !ring_sizes || n_rings <= 0 || n_rings > 4096 || stride < 3)
+        return fail(c, IMLS_ERR_ARG, "bad curvature params / ring sizes / stride");
+    if (p->window_size < 0) return fail(c, IMLS_ERR_ARG, "bad curvature window_size");
+    if (n_rows > 0 && (!row_index || !row_flags || !candidates_out || !n_cand))
+        return fail(c, IMLS_ERR_ARG, "null row arrays / candidate outputs");
+    long long total = 0;
+    for (int i = 0; i < n_rings; ++i) total += ring_sizes[i];
+    if (total > 0 && !xyz) return fail(c, IMLS_ERR_ARG, "null xyz");
+    if (total >= (1ll << 31) || n_rows >= ((size_t)1 << 31)) return fail(c, IMLS_ERR_CAPACITY, "cloud too large");
+    if (int rc = check_device(c)) return rc;
+    int slot = -1;
+    hipEvent_t marks[2];
+    hipEvent_t* mk = nullptr;
+    if (c->timing && (slot = ev_pair(c)) >= 0) {
+        marks[0] = c->ev[slot];
+        marks[1] = c->ev[slot + 1];
+        mk = marks;
+    }
+    int rc = presample_curvature_run(c->stream, *p, xyz, stride, ring_sizes, n_rings, row_index, row_flags, n_rows,
+                                     c->curv_mem, mk, curvature_out, candidates_out, n_cand, c->err);
+    if (mk && rc == IMLS_OK && total > 0) c->ev_pairs[10].push_back({slot, slot + 1});   // (an empty cloud records nothing)
+    if (c->timing) harvest_timing(c);
+    return rc;
+}
+
+int imls_sample_three_axis(imls_ctx* c, int32_t points_per_list, const float* xyz, const float* nrm, size_t stride,
+                           size_t n, const float* evals, const int32_t* candidates, size_t n_cand, int32_t* sampled_out,
+                           size_t* n_sampled, uint64_t* nan_keys) {
+    if (!c) return IMLS_ERR_ARG;
+    if (points_per_list < 1 || points_per_list > 4096)
+        return fail(c, IMLS_ERR_UNSUPPORTED,
+                    "three_axis: points_per_list must be in [1, 4096] (points_per_list = " + std::to_string(points_per_list) + ")");
+    if (stride < 3 || !n_sampled || (n_cand > 0 && (!xyz || !nrm || !evals || !candidates || !sampled_out)))
+        return fail(c, IMLS_ERR_ARG, "three_axis: null array or stride < 3");
+    if (n >= (1ull << 31) || n_cand >= (1ull << 31) / 9) return fail(c, IMLS_ERR_CAPACITY, "cloud too large");
+    if (int rc = check_device(c)) return rc;
+    int slot = -1;
+    hipEvent_t marks[2];
+    hipEvent_t* mk = nullptr;
+    if (c->timing && n_cand > 0 && (slot = ev_pair(c)) >= 0) {
+        marks[0] = c->ev[slot];
+        marks[1] = c->ev[slot + 1];
+        mk = marks;
+    }
+    int rc = three_axis_run(c->stream, points_per_list, xyz, nrm, stride, n, evals, candidates, n_cand, c->ta_mem, mk,
+                            sampled_out, n_sampled, nan_keys, c->err);
+    if (mk && rc == IMLS_OK) c->ev_pairs[9].push_back({slot, slot + 1});
+    if (c->timing) harvest_timing(c);
+    return rc;
+}
+
+int imls_sample_random(imls_ctx* c, const int32_t* candidates, size_t n_cand, int32_t max_points, uint32_t shuffle_seed,
+                       int32_t* sampled_out, size_t* n_sampled) {
+    if (!c) return IMLS_ERR_ARG;
+    if (max_points < 0 || !n_sampled || (n_cand > 0 && (!candidates || (max_points > 0 && !sampled_out))))
+        return fail(c, IMLS_ERR_ARG, "random: null array or max_points < 0");
+    if (n_cand >= (1ull << 31)) return fail(c, IMLS_ERR_CAPACITY, "too many candidates");
+    sample_random_host(candidates, n_cand, max_points, shuffle_seed, sampled_out, n_sampled);
+    return IMLS_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

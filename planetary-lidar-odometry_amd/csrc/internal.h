@@ -515,5 +515,19 @@ int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_ho
 int sample_run(hipStream_t s, const imls_sample_params& p, const float* xyz, const float* nrm, size_t stride, size_t n,
                const int32_t* cand, size_t n_cand, const float* last_xyz, size_t last_stride, size_t m, DevBuf& mem,
                hipEvent_t* marks, int32_t* sampled_out, size_t* n_sampled, float* bin_weights_out, std::string& err);
+// randomSampling (566-582) alone: the first min(max_points, n_cand) entries of the seeded shuffle
+void sample_random_host(const int32_t* cand, size_t n_cand, int32_t max_points, uint32_t shuffle_seed,
+                        int32_t* sampled_out, size_t* n_sampled);
+
+// presample.hip — curvature presample (imls_presample_curvature)
+int presample_curvature_run(hipStream_t s, const imls_curvature_params& p, const float* xyz, size_t stride,
+                            const int32_t* sizes, int n_rings, const uint32_t* row_index, const uint8_t* row_flags,
+                            size_t n_rows, DevBuf& mem, hipEvent_t* marks, float* curvature_out, int32_t* candidates_out,
+                            size_t* n_cand, std::string& err);
+
+// three_axis.hip — threeAxisSampling (imls_sample_three_axis)
+int three_axis_run(hipStream_t s, int points_per_list, const float* xyz, const float* nrm, size_t stride, size_t n,
+                   const float* evals, const int32_t* cand, size_t n_cand, DevBuf& mem, hipEvent_t* marks,
+                   int32_t* sampled_out, size_t* n_sampled, uint64_t* nan_keys, std::string& err);
 
 }  // namespace imlsgpu

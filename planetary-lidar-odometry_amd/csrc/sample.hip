@@ -399,4 +399,14 @@ int sample_run(hipStream_t s, const imls_sample_params& p, const float* xyz, con
     return IMLS_OK;
 }
 
+// samplePointCloud "random" (779-781): one randomSampling call over all candidates
+void sample_random_host(const int32_t* cand, size_t n_cand, int32_t max_points, uint32_t shuffle_seed,
+                        int32_t* sampled_out, size_t* n_sampled) {
+    HostRng rng{shuffle_seed};
+    std::vector<int> out;
+    rng.shuffle_take(std::vector<int>(cand, cand + n_cand), max_points, out);
+    std::copy(out.begin(), out.end(), sampled_out);
+    if (n_sampled) *n_sampled = out.size();
+}
+
 }  // namespace imlsgpu

@@ -362,6 +362,54 @@ class ImlsContext:
                                                      _ptr(out), C.byref(k), _ptr(w)))
         return out[:k.value], w
 
+    def presample_curvature(self, xyz, ring_sizes, row_index, row_flags,
+                            curvature_params: Optional[_abi.ImlsCurvatureParams] = None):
+        """The "curvature" presample (scan_registration.cpp:1071-1113, 1462-1473, 1481-1489) on the
+        ring-concatenated cloud `laserCloud` and the rows ring_normals_pca returned for it (its
+        `index` and `flags`).  Returns (per-point curvature (n,), candidate rows ascending)."""
+        a = np.ascontiguousarray(xyz, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("xyz must be (n, >=3)")
+        rs = np.ascontiguousarray(ring_sizes, dtype=np.int32)
+        if int(rs.sum()) != a.shape[0]:
+            raise ValueError("ring sizes must sum to the number of points")
+        ri = np.ascontiguousarray(row_index, dtype=np.uint32)
+        rf = np.ascontiguousarray(row_flags, dtype=np.uint8)
+        if ri.shape != rf.shape or ri.ndim != 1:
+            raise ValueError("row_index and row_flags must be 1-D and of equal length")
+        p = curvature_params if curvature_params is not None else _abi.default_curvature_params()
+        curv = np.zeros(max(a.shape[0], 1), np.float32); cand = np.zeros(max(len(ri), 1), np.int32); k = C.c_size_t()
+        self._check(self.lib.imls_presample_curvature(self.ctx, C.byref(p), _ptr(a), a.shape[1], _ptr(rs), len(rs),
+                                                      _ptr(ri), _ptr(rf), len(ri), _ptr(curv), _ptr(cand), C.byref(k)))
+        return curv[:a.shape[0]], cand[:k.value]
+
+    def sample_three_axis(self, xyz, nrm, evals, candidates, points_per_list: int = 200):
+        """samplePointCloud "three_axis" (scan_registration.cpp:492-533) of the filtered cloud (xyz,
+        nrm: (n, 3) float32; evals: (n, 3) = ring_normals_pca's `evals`) restricted to the distinct
+        `candidates`.  Returns (sampled indices: nine lists of min(points_per_list, len(candidates))
+        each, in list order; the number of NaN-valued entries, which rank last in their list)."""
+        a = np.ascontiguousarray(np.asarray(xyz, np.float32)[:, :3])
+        nn = np.ascontiguousarray(np.asarray(nrm, np.float32)[:, :3])
+        ev = np.ascontiguousarray(np.asarray(evals, np.float32).reshape(-1, 3))
+        if a.shape != nn.shape or ev.shape != a.shape:
+            raise ValueError("xyz, nrm and evals must all be (n, 3)")
+        cand = np.ascontiguousarray(candidates, dtype=np.int32)
+        out = np.zeros(9 * max(min(int(points_per_list), len(cand)), 1), np.int32)
+        k = C.c_size_t(); nan = C.c_uint64()
+        self._check(self.lib.imls_sample_three_axis(self.ctx, int(points_per_list), _ptr(a), _ptr(nn), 3, a.shape[0],
+                                                    _ptr(ev), _ptr(cand), len(cand), _ptr(out), C.byref(k),
+                                                    C.byref(nan)))
+        return out[:k.value], int(nan.value)
+
+    def sample_random(self, candidates, max_points: int = 2000, shuffle_seed: int = 0) -> np.ndarray:
+        """samplePointCloud "random" (scan_registration.cpp:566-582, 779-781): the first
+        min(max_points, len(candidates)) entries of the candidates shuffled by std::mt19937(shuffle_seed)."""
+        cand = np.ascontiguousarray(candidates, dtype=np.int32)
+        out = np.zeros(max(min(int(max_points), len(cand)), 1), np.int32); k = C.c_size_t()
+        self._check(self.lib.imls_sample_random(self.ctx, _ptr(cand), len(cand), int(max_points),
+                                                int(shuffle_seed) & 0xFFFFFFFF, _ptr(out), C.byref(k)))
+        return out[:k.value]
+
     def enable_stats(self, on=True):
         """Collect the traversal / neighbour counters (traversal_stats, index_stats' sum_kq / nn_found)."""
         self._check(self.lib.imls_enable_stats(self.ctx, int(on)))

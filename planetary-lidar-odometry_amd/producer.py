@@ -1,6 +1,8 @@
 """Upstream producer for the registration path: scan_registration.cpp's per-sweep chain for the
 shipped config (config.json scan_registration: compute_normal_method "pca" → presample_method
-"geometric_features" → sample_method "major_axis"), on the GPU through the C ABI.
+"geometric_features" → sample_method "major_axis") and the other configurations the reference marks
+as verified (presample_method "curvature"; sample_method "normal", "three_axis", "random"), on the
+GPU through the C ABI.
 
   ScanRegistration.process_raw(raw) the whole handler: scan_front_end (NaN / range filter, ring
                                     assignment and relative time, 862-1069) → process
@@ -16,6 +18,7 @@ with the "normal" method (frame == 1, 783) and every later one against the previ
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -25,30 +28,67 @@ from .imls_icp import ImlsContext
 from .synth import POINT_DTYPE
 
 
+SAMPLE_METHODS = ("major_axis", "normal", "three_axis", "random")
+PRESAMPLE_METHODS = ("geometric_features", "curvature")
+
+
 class ScanRegistration:
     def __init__(self, ctx: Optional[ImlsContext] = None, device: int = 0,
                  pca_params: Optional[_abi.ImlsPcaParams] = None, sample_method: str = "major_axis",
-                 shuffle_seed: int = 0, rand_seed: int = 1):
-        if sample_method not in ("major_axis", "normal"):
-            raise ValueError(f"sample_method {sample_method!r}: the GPU producer ships 'major_axis' and 'normal'")
+                 shuffle_seed: int = 0, rand_seed: int = 1, presample_method: str = "geometric_features",
+                 curvature_params: Optional[_abi.ImlsCurvatureParams] = None, points_per_list: int = 200,
+                 max_points: int = 2000, normal_params: Optional[_abi.ImlsSampleParams] = None,
+                 major_axis_params: Optional[_abi.ImlsSampleParams] = None):
+        if sample_method not in SAMPLE_METHODS:
+            raise ValueError(f"sample_method {sample_method!r}: the GPU producer ships {', '.join(SAMPLE_METHODS)}")
+        if presample_method not in PRESAMPLE_METHODS:
+            raise ValueError(f"presample_method {presample_method!r}: the GPU producer ships "
+                             f"{', '.join(PRESAMPLE_METHODS)}")
+        if not 1 <= int(points_per_list) <= _abi.THREE_AXIS_MAX_POINTS_PER_LIST:
+            raise ValueError(f"points_per_list {points_per_list}: must be in [1, {_abi.THREE_AXIS_MAX_POINTS_PER_LIST}]")
         self._own = ctx is None
-        self.ctx = ctx if ctx is not None else ImlsContext(device=device)
+        self._ctx = ctx                     # an owned context is created at its first use
+        self._device = device
         self.pca_params = pca_params if pca_params is not None else _abi.default_pca_params()
         self.sample_method = sample_method
+        self.presample_method = presample_method
+        self.curvature_params = curvature_params if curvature_params is not None else _abi.default_curvature_params()
+        self.points_per_list = int(points_per_list)        # sample_method.three_axis.points_per_list
+        self.max_points = int(max_points)                  # sample_method.random.max_points
+        self.normal_params = normal_params                 # sample_method.normal / .major_axis blocks
+        self.major_axis_params = major_axis_params         # (None: the shipped values)
         self.shuffle_seed = shuffle_seed
         self.rand_seed = rand_seed
         self.frame = 1                      # scan_registration.cpp:64
         self.last_xyz: Optional[np.ndarray] = None
         self.last_pca: Optional[dict] = None
+        self.last_curvature: Optional[np.ndarray] = None   # per laserCloud point (curvature presample)
+        self.last_candidates: Optional[np.ndarray] = None
+        self.last_sampled: Optional[np.ndarray] = None
+
+    @property
+    def ctx(self) -> ImlsContext:
+        if self._ctx is None:
+            self._ctx = ImlsContext(device=self._device)
+        return self._ctx
 
     def close(self):
-        if self._own:
-            self.ctx.close()
+        if self._own and self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+
+    def _frame_seed(self) -> int:
+        return (self.shuffle_seed + 7919 * self.frame) & 0xFFFFFFFF
 
     def sample_params(self) -> _abi.ImlsSampleParams:
         first = self.sample_method == "normal" or self.frame == 1
-        sp = _abi.default_sample_params(_abi.IMLS_SAMPLE_NORMAL if first else _abi.IMLS_SAMPLE_MAJOR_AXIS)
-        sp.shuffle_seed = (self.shuffle_seed + 7919 * self.frame) & 0xFFFFFFFF
+        method = _abi.IMLS_SAMPLE_NORMAL if first else _abi.IMLS_SAMPLE_MAJOR_AXIS
+        sp = _abi.default_sample_params(method)
+        given = self.normal_params if first else self.major_axis_params
+        if given is not None:
+            C.memmove(C.byref(sp), C.byref(given), C.sizeof(sp))
+            sp.method = method
+        sp.shuffle_seed = self._frame_seed()
         sp.rand_seed = (self.rand_seed + self.frame - 1) & 0xFFFFFFFF
         return sp
 
@@ -69,13 +109,25 @@ class ScanRegistration:
         cloud["normal_x"], cloud["normal_y"], cloud["normal_z"] = o["normal"][:, 0], o["normal"][:, 1], o["normal"][:, 2]
         if intensity is not None:
             cloud["intensity"] = np.asarray(intensity, np.float32)[idx]
-        cand = np.nonzero(o["flags"] & _abi.IMLS_PCA_CANDIDATE)[0].astype(np.int32)
+        if self.presample_method == "curvature":           # 1071-1113, 1462-1473, 1481-1489
+            curv, cand = self.ctx.presample_curvature(xyz, ring_sizes, o["index"], o["flags"], self.curvature_params)
+            cloud["curvature"] = curv[idx]                 # 1220
+            self.last_curvature = curv
+        else:
+            cand = np.nonzero(o["flags"] & _abi.IMLS_PCA_CANDIDATE)[0].astype(np.int32)
         fxyz = np.stack([cloud["x"], cloud["y"], cloud["z"]], 1)
-        sampled, _ = self.ctx.sample_point_cloud(fxyz, o["normal"], cand, self.last_xyz, self.sample_params())
+        if self.sample_method == "three_axis":             # 769-773
+            sampled, _ = self.ctx.sample_three_axis(fxyz, o["normal"], o["evals"], cand, self.points_per_list)
+        elif self.sample_method == "random":               # 779-781
+            sampled = self.ctx.sample_random(cand, self.max_points, self._frame_seed())
+        else:
+            sampled, _ = self.ctx.sample_point_cloud(fxyz, o["normal"], cand, self.last_xyz, self.sample_params())
         surface = cloud[sampled]
         self.frame += 1
         self.last_xyz = fxyz
         self.last_pca = o
+        self.last_candidates = cand
+        self.last_sampled = sampled
         return cloud, surface
 
 
