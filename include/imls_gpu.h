@@ -555,6 +555,95 @@ int imls_sample_three_axis(imls_ctx* ctx, int32_t points_per_list, const float* 
 int imls_sample_random(imls_ctx* ctx, const int32_t* candidates, size_t n_cand, int32_t max_points,
                        uint32_t shuffle_seed, int32_t* sampled_out, size_t* n_sampled);
 
+/* ---- upstream producer: a raw sweep to the two clouds, on the device ---------------------- */
+/* laserCloudHandler as one call (scan_registration.cpp:809-1503): front end → ring PCA → presample →
+ * sampling, every cloud staying in HBM.  imls_default_sweep_params() fills the shipped chain
+ * (pca → geometric_features → major_axis) from the defaults of its parts. */
+typedef enum imls_presample_method {
+    IMLS_PRESAMPLE_GEOMETRIC_FEATURES = 0,
+    IMLS_PRESAMPLE_CURVATURE = 1
+} imls_presample_method;
+typedef enum imls_sweep_sample_method {
+    IMLS_SWEEP_MAJOR_AXIS = 0,      /* the "normal" block on sweep 1, the "major_axis" block afterwards (783) */
+    IMLS_SWEEP_NORMAL = 1,
+    IMLS_SWEEP_THREE_AXIS = 2,
+    IMLS_SWEEP_RANDOM = 3
+} imls_sweep_sample_method;
+typedef struct imls_sweep_params {
+    imls_front_params front;
+    imls_pca_params pca;
+    imls_curvature_params curvature;
+    imls_sample_params normal;      /* sample_method.normal (its method / seeds fields are not read) */
+    imls_sample_params major_axis;  /* sample_method.major_axis (likewise) */
+    int32_t presample_method;       /* imls_presample_method */
+    int32_t sample_method;          /* imls_sweep_sample_method */
+    int32_t points_per_list;        /* three_axis.points_per_list = 200 */
+    int32_t max_points;             /* random.max_points = 2000 */
+    uint32_t shuffle_seed;          /* this call's seeds, used as given (imls_sample_params.shuffle_seed, */
+    uint32_t rand_seed;             /* .rand_seed; imls_sample_random's shuffle_seed) */
+} imls_sweep_params;
+void imls_default_sweep_params(imls_sweep_params* p);
+
+typedef struct imls_sweep_info {
+    uint64_t sweep;                 /* the sweep counter this call ran with (1 = first) */
+    uint64_t n_input, n_front;      /* points given; laserCloud points after the front end */
+    uint64_t n_filtered;            /* rows of pcl_cloud */
+    uint64_t n_candidates;          /* presample candidates */
+    uint64_t n_flat;                /* rows of pcl_surface_cloud */
+    uint64_t pca_failure, plane_invalid;   /* imls_ring_normals_pca's counters */
+    uint64_t nan_keys;              /* imls_sample_three_axis's nan_keys */
+    uint64_t nan_normals;           /* candidates left out of the spherical histogram (below) */
+    uint64_t bytes_h2d, bytes_d2h;  /* bytes this call copied host → device / device → host */
+    uint64_t host_syncs;            /* times this call waited for the stream */
+} imls_sweep_info;
+
+/* One sweep: xyz (host) is uploaded once as given (n·stride_floats floats); the _device form reads
+ * the same records from HBM.  The context keeps the sweep counter of scan_registration.cpp:64 (1 at
+ * creation, +1 per successful call, imls_sweep_reset → 1 and the previous cloud forgotten):
+ * IMLS_SWEEP_MAJOR_AXIS samples with the `normal` block iff the counter is 1, later sweeps against the
+ * previous sweep's pcl_cloud, which stays on the device.  The result is that of imls_scan_front_end →
+ * imls_ring_normals_pca → (imls_presample_curvature) → imls_sample_point_cloud / _three_axis / _random
+ * on the same inputs, with one definition of its own: a candidate whose normal gives no histogram
+ * bin (a non-finite component, |nz| > 1) indexes outside the histogram in the reference; here it is
+ * left out of the sampling and counted in info->nan_normals.  The spherical histogram must have at most
+ * 4096 bins, else IMLS_ERR_UNSUPPORTED.  Besides the sweep itself only tables go up (ring offsets, the
+ * PCA block table, shuffled positions, the rand() state) and only control words come down (ring
+ * sizes, stage counts, bin sizes); info (nullable) reports the figures.  An empty sweep, or one the
+ * filters empty, gives two empty clouds and IMLS_OK.
+ *
+ * Lifetime of the clouds: complete on return; valid and unchanged until the SECOND-next
+ * imls_sweep_process[_device] / imls_sweep_reset on this context (two buffer sets rotate), so the
+ * clouds of sweep k may be read by work enqueued on other streams while sweep k+1 is produced.  With
+ * max_queue_size 1 imls_map_push_device indexes the pushed scan through its NaN filter at the push;
+ * the same pcl_cloud is the next sweep's previous cloud. */
+int imls_sweep_process(imls_ctx* ctx, const imls_sweep_params* p, const float* xyz, size_t stride_floats, size_t n,
+                       imls_sweep_info* info);
+int imls_sweep_process_device(imls_ctx* ctx, const imls_sweep_params* p, const float* d_xyz, size_t stride_floats,
+                              size_t n, imls_sweep_info* info);
+int imls_sweep_reset(imls_ctx* ctx);
+/* The last sweep's clouds as SoA float32[6][n] (x, y, z, nx, ny, nz rows: what imls_set_source_device
+ * and imls_map_push_device take), and pcl_cloud's intensity and curvature [n_filtered] (each output
+ * nullable; null pointers for an empty cloud).  IMLS_ERR_STATE before the first sweep. */
+int imls_sweep_clouds_device(imls_ctx* ctx, const float** d_filtered_soa6, size_t* n_filtered, const float** d_flat_soa6,
+                             size_t* n_flat, const float** d_intensity, const float** d_curvature);
+/* The last sweep's pcl_cloud (which = 0) or pcl_surface_cloud (which = 1) as 48-byte
+ * pcl::PointXYZINormal records (imls_wire.hpp's layout; `records` nullable, capacity `cap` records,
+ * IMLS_ERR_CAPACITY when smaller than *n); sampled_index (nullable, which = 1): the pcl_cloud row of
+ * every pcl_surface_cloud record. */
+int imls_sweep_download(imls_ctx* ctx, int32_t which, void* records, size_t cap, size_t* n, int32_t* sampled_index);
+/* imls_sample_point_cloud on device inputs — the sampler stage of imls_sweep_process alone:
+ * d_soa6 [6][n] pcl_cloud, d_candidates [n_cand], d_last_soa6 [6][m] (rows x, y, z read; major_axis),
+ * d_sampled_out (capacity n_cand + bins), d_bin_weights_out (nullable, bins floats), nan_normals
+ * (nullable).  Results: those of imls_sample_point_cloud (and the nan_normals definition above). */
+int imls_sample_point_cloud_device(imls_ctx* ctx, const imls_sample_params* p, const float* d_soa6, size_t n,
+                                   const int32_t* d_candidates, size_t n_cand, const float* d_last_soa6, size_t m,
+                                   int32_t* d_sampled_out, size_t* n_sampled, float* d_bin_weights_out,
+                                   uint64_t* nan_normals);
+/* randomSampling's shuffle as positions (host only, no context): the first min(k, size) entries of
+ * 0 … size−1 shuffled by std::shuffle with std::mt19937(seed) — std::shuffle permutes positions
+ * whatever the contents, so bin[out[i]] is the shuffled bin. */
+void imls_shuffle_positions(uint32_t seed, int32_t size, int32_t k, int32_t* out, size_t* n_out);
+
 /* ---- nearest-neighbour queries ---------------------------------------------------------- */
 /* Replaces a Nabo::NNSearchD::knn call (imls_icp.cpp:197, 372, 414, 605, 650;
  * laser_odometry.cpp:348) with epsilon = 0 and SORT_RESULTS on the index the context already holds:
@@ -631,7 +720,9 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * exact fallback of each chunk; the queries' ordering is not included, as the source's is not in 0;
  * imls_knn_device's events are read by the next call that synchronises, e.g. imls_knn),
  * 9 = imls_sample_three_axis (keys and per-list top-k), 10 = imls_presample_curvature (stencil and
- * candidate compaction).  enable: 0 off, 1 every kind above (the members of
+ * candidate compaction), 11 = the sampler, compaction and cloud-assembly kernels of imls_sweep_process /
+ * imls_sample_point_cloud_device (which record 5, 6, 7, 9 and 10 for the kernels they share with
+ * the calls above).  enable: 0 off, 1 every kind above (the members of
  * an imls_register_frames batch then build their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */

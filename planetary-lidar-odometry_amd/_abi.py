@@ -176,6 +176,46 @@ def default_curvature_params() -> ImlsCurvatureParams:
 
 THREE_AXIS_MAX_POINTS_PER_LIST = 4096   # imls_sample_three_axis: points_per_list in [1, 4096]
 
+IMLS_PRESAMPLE_GEOMETRIC_FEATURES, IMLS_PRESAMPLE_CURVATURE = 0, 1
+IMLS_SWEEP_MAJOR_AXIS, IMLS_SWEEP_NORMAL, IMLS_SWEEP_THREE_AXIS, IMLS_SWEEP_RANDOM = 0, 1, 2, 3
+PRESAMPLE_IDS = {"geometric_features": IMLS_PRESAMPLE_GEOMETRIC_FEATURES, "curvature": IMLS_PRESAMPLE_CURVATURE}
+SWEEP_SAMPLE_IDS = {"major_axis": IMLS_SWEEP_MAJOR_AXIS, "normal": IMLS_SWEEP_NORMAL,
+                    "three_axis": IMLS_SWEEP_THREE_AXIS, "random": IMLS_SWEEP_RANDOM}
+
+
+class ImlsSweepParams(C.Structure):
+    """imls_sweep_params (include/imls_gpu.h): the whole producer chain of one imls_sweep_process."""
+    _fields_ = [("front", ImlsFrontParams), ("pca", ImlsPcaParams), ("curvature", ImlsCurvatureParams),
+                ("normal", ImlsSampleParams), ("major_axis", ImlsSampleParams),
+                ("presample_method", _i32), ("sample_method", _i32), ("points_per_list", _i32), ("max_points", _i32),
+                ("shuffle_seed", _u32), ("rand_seed", _u32)]
+
+
+class ImlsSweepInfo(C.Structure):
+    """imls_sweep_info (include/imls_gpu.h): counts and transfer accounting of one sweep."""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "sweep", "n_input", "n_front", "n_filtered", "n_candidates", "n_flat", "pca_failure", "plane_invalid",
+        "nan_keys", "nan_normals", "bytes_h2d", "bytes_d2h", "host_syncs")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def default_sweep_params() -> ImlsSweepParams:
+    """The shipped chain pca → geometric_features → major_axis (imls_default_sweep_params() in the
+    library), computed here so CPU-only code needs no library."""
+    p = ImlsSweepParams()
+    p.front.n_scans, p.front.minimum_range, p.front.maximum_range = 64, 2.0, 150.0
+    p.front.scan_period, p.front.is_dense = 0.1, 0
+    p.pca = default_pca_params()
+    p.curvature = default_curvature_params()
+    p.normal = default_sample_params(IMLS_SAMPLE_NORMAL)
+    p.major_axis = default_sample_params(IMLS_SAMPLE_MAJOR_AXIS)
+    p.presample_method, p.sample_method = IMLS_PRESAMPLE_GEOMETRIC_FEATURES, IMLS_SWEEP_MAJOR_AXIS
+    p.points_per_list, p.max_points = 200, 2000
+    p.shuffle_seed, p.rand_seed = 0, 1
+    return p
+
 
 class ImlsPairInput(C.Structure):
     """imls_pair_input (include/imls_gpu.h)."""
@@ -184,7 +224,7 @@ class ImlsPairInput(C.Structure):
                 ("stride_floats", C.c_size_t)]
 
 
-def _bind(lib: C.CDLL) -> C.CDLL:
+def _bind(lib: C.CDLL, strict: bool = True) -> C.CDLL:
     P, VP, SZ = C.POINTER, C.c_void_p, C.c_size_t
     sig = {
         "imls_abi_version": (C.c_int, []),
@@ -254,8 +294,19 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "imls_sample_random": (C.c_int, [VP, VP, SZ, C.c_int32, C.c_uint32, VP, P(SZ)]),
         "imls_knn": (C.c_int, [VP, VP, SZ, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
         "imls_knn_device": (C.c_int, [VP, VP, SZ, C.c_int32, C.c_double, C.c_uint32, VP, VP, VP]),
+        "imls_default_sweep_params": (None, [P(ImlsSweepParams)]),
+        "imls_sweep_process": (C.c_int, [VP, P(ImlsSweepParams), VP, SZ, SZ, P(ImlsSweepInfo)]),
+        "imls_sweep_process_device": (C.c_int, [VP, P(ImlsSweepParams), VP, SZ, SZ, P(ImlsSweepInfo)]),
+        "imls_sweep_reset": (C.c_int, [VP]),
+        "imls_sweep_clouds_device": (C.c_int, [VP, P(VP), P(SZ), P(VP), P(SZ), P(VP), P(VP)]),
+        "imls_sweep_download": (C.c_int, [VP, C.c_int32, VP, SZ, P(SZ), VP]),
+        "imls_sample_point_cloud_device": (C.c_int, [VP, P(ImlsSampleParams), VP, SZ, VP, SZ, VP, SZ, VP, P(SZ), VP,
+                                                     P(C.c_uint64)]),
+        "imls_shuffle_positions": (None, [C.c_uint32, C.c_int32, C.c_int32, VP, P(SZ)]),
     }
     for name, (res, args) in sig.items():
+        if not strict and not hasattr(lib, name):
+            continue                # an older diagnostic build: calling the missing entry point raises AttributeError
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -279,6 +330,8 @@ ABI_SYMBOLS = (
     "imls_captured_correspondences", "imls_set_option", "imls_get_option", "imls_knn", "imls_knn_device",
     "imls_set_initial_pose", "imls_map_push_posed", "imls_map_push_posed_device", "imls_map_rebase",
     "imls_default_curvature_params", "imls_presample_curvature", "imls_sample_three_axis", "imls_sample_random",
+    "imls_default_sweep_params", "imls_sweep_process", "imls_sweep_process_device", "imls_sweep_reset",
+    "imls_sweep_clouds_device", "imls_sweep_download", "imls_sample_point_cloud_device", "imls_shuffle_positions",
 )
 
 _LIB = None
@@ -293,7 +346,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     p = pathlib.Path(path) if path else pathlib.Path(os.environ.get("IMLS_LIB_PATH", LIB_PATH))
     if not p.exists():
         raise RuntimeError(f"HIP extension missing: {p} (run __graft_entry__.build())")
-    lib = _bind(C.CDLL(str(p)))
+    # the product library must export every entry point; a build named by IMLS_LIB_PATH (another
+    # commit's library in an A/B run) may predate some
+    lib = _bind(C.CDLL(str(p)), strict=p == LIB_PATH)
     if path is None:
         _LIB = lib
     return lib

@@ -139,8 +139,8 @@ void release_retired(int device) {
 }
 }  // namespace imlsgpu
 
-constexpr int kTimingKinds = 11;  // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query,
-                                  // three_axis sampling, curvature presample
+constexpr int kTimingKinds = 12;  // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query,
+                                  // three_axis sampling, curvature presample, sweep sampler / assembly
 
 // Runtime options of a context (imls_set_option; include/imls_gpu.h documents each): the validated
 // tuning parameters and test hooks.  Nothing is read from the environment.
@@ -223,6 +223,7 @@ struct imls_ctx {
     DevBuf front_mem;                     // imls_scan_front_end scratch
     DevBuf curv_mem;                      // imls_presample_curvature scratch
     DevBuf ta_mem;                        // imls_sample_three_axis scratch
+    SweepState sweep;                     // imls_sweep_process: the rotating cloud sets, counter, scratch
     // imls_knn / imls_knn_device: buffers of their own (one chunk of ≤ kKnnChunk queries), so a query
     // leaves the loaded source, its order, the correspondences and the neighbour lists alone —
     // queries (xyz, non-finite flag), their Morton order + the sort's scratch, the list block,
@@ -1295,6 +1296,8 @@ void imls_destroy(imls_ctx* c) {
                       &c->upload_t, &c->spt, &c->snr, &c->sscratch,
                       &c->upload_s, &c->cs, &c->cd, &c->cn, &c->solve_mem, &c->trace_mem, &c->stats, &c->rows_d, &c->pose_tmp};
     for (DevBuf* b : bufs)
+        if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : sweep_buffers(c->sweep))
         if (b->p) (void)hipFree(b->p);
     for (auto* v : {&c->fifo}) for (auto& sl : *v) for (DevBuf* b : {&sl.buf, &sl.fpt, &sl.fnr, &sl.run}) if (b->p) (void)hipFree(b->p);
     for (auto& sl : c->slot_pool) for (DevBuf* b : {&sl.buf, &sl.fpt, &sl.fnr, &sl.run}) if (b->p) (void)hipFree(b->p);
@@ -2669,6 +2672,136 @@ int imls_sample_random(imls_ctx* c, const int32_t* candidates, size_t n_cand, in
     if (n_cand >= (1ull << 31)) return fail(c, IMLS_ERR_CAPACITY, "too many candidates");
     sample_random_host(candidates, n_cand, max_points, shuffle_seed, sampled_out, n_sampled);
     return IMLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A raw sweep to the two clouds on the device (sweep.hip)
+// ---------------------------------------------------------------------------------------------
+void imls_default_sweep_params(imls_sweep_params* p) {
+    if (!p) return;
+    imls_default_front_params(&p->front);
+    imls_default_pca_params(&p->pca);
+    imls_default_curvature_params(&p->curvature);
+    imls_default_sample_params(&p->normal, IMLS_SAMPLE_NORMAL);
+    imls_default_sample_params(&p->major_axis, IMLS_SAMPLE_MAJOR_AXIS);
+    p->presample_method = IMLS_PRESAMPLE_GEOMETRIC_FEATURES;
+    p->sample_method = IMLS_SWEEP_MAJOR_AXIS;
+    p->points_per_list = 200;
+    p->max_points = 2000;
+    p->shuffle_seed = 0;
+    p->rand_seed = 1;
+}
+
+}  // extern "C"
+namespace {
+
+// SweepMark: an event pair harvested as `kind` (timing level 1 only)
+bool sweep_mark(void* owner, int kind, hipEvent_t ev[2]) {
+    imls_ctx* c = (imls_ctx*)owner;
+    if (c->timing != 1) return false;
+    const int slot = ev_pair(c);
+    if (slot < 0) return false;
+    ev[0] = c->ev[slot];
+    ev[1] = c->ev[slot + 1];
+    c->ev_pairs[kind].push_back({slot, slot + 1});
+    return true;
+}
+SweepEnv sweep_env(imls_ctx* c) { return SweepEnv{c->stream, &c->front_mem, &c->pca_mem, sweep_mark, c, &c->err}; }
+
+int sweep_process(imls_ctx* c, const imls_sweep_params* p, const float* h_xyz, const float* d_xyz, size_t stride, size_t n,
+                  imls_sweep_info* info) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!p || (n > 0 && ((!h_xyz && !d_xyz) || stride < 3))) return fail(c, IMLS_ERR_ARG, "sweep: null params / sweep or stride < 3");
+    if (p->presample_method < 0 || p->presample_method > 1 || p->sample_method < 0 || p->sample_method > 3)
+        return fail(c, IMLS_ERR_ARG, "sweep: unknown presample / sample method");
+    if (p->pca.window_size < 0 || p->pca.iter_step <= 0 || p->pca.neighbor_scan < 0 || p->pca.neighbor_scan > 1)
+        return fail(c, IMLS_ERR_ARG, "bad pca window_size / iter_step / neighbor_scan");
+    if (p->presample_method == IMLS_PRESAMPLE_CURVATURE && p->curvature.window_size < 0)
+        return fail(c, IMLS_ERR_ARG, "bad curvature window_size");
+    if (p->sample_method == IMLS_SWEEP_THREE_AXIS && (p->points_per_list < 1 || p->points_per_list > 4096))
+        return fail(c, IMLS_ERR_UNSUPPORTED, "three_axis: points_per_list must be in [1, 4096]");
+    if (p->sample_method == IMLS_SWEEP_RANDOM && p->max_points < 0) return fail(c, IMLS_ERR_ARG, "random: max_points < 0");
+    if (int rc = check_device(c)) return rc;
+    SweepEnv e = sweep_env(c);
+    const int rc = sweep_run(e, c->sweep, *p, h_xyz, d_xyz, stride, n, info);
+    if (c->timing) {
+        if (rc != IMLS_OK) (void)hipStreamSynchronize(c->stream);
+        harvest_timing(c);
+    }
+    return rc;
+}
+
+}  // namespace
+extern "C" {
+
+int imls_sweep_process(imls_ctx* c, const imls_sweep_params* p, const float* xyz, size_t stride_floats, size_t n,
+                       imls_sweep_info* info) {
+    return sweep_process(c, p, xyz, nullptr, stride_floats, n, info);
+}
+
+int imls_sweep_process_device(imls_ctx* c, const imls_sweep_params* p, const float* d_xyz, size_t stride_floats, size_t n,
+                              imls_sweep_info* info) {
+    return sweep_process(c, p, nullptr, d_xyz, stride_floats, n, info);
+}
+
+int imls_sweep_reset(imls_ctx* c) {
+    if (!c) return IMLS_ERR_ARG;
+    c->sweep.counter = 1;
+    c->sweep.has = false;
+    c->sweep.cur = 0;
+    for (auto& S : c->sweep.set) S.n_filtered = S.n_flat = S.cap_filtered = 0;
+    return IMLS_OK;
+}
+
+int imls_sweep_clouds_device(imls_ctx* c, const float** d_filtered_soa6, size_t* n_filtered, const float** d_flat_soa6,
+                             size_t* n_flat, const float** d_intensity, const float** d_curvature) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!c->sweep.has) return fail(c, IMLS_ERR_STATE, "no sweep processed yet");
+    const SweepSet& S = c->sweep.set[c->sweep.cur];
+    const float* side = S.n_filtered ? (const float*)S.side.p : nullptr;
+    if (d_filtered_soa6) *d_filtered_soa6 = S.n_filtered ? (const float*)S.soa6.p : nullptr;
+    if (n_filtered) *n_filtered = S.n_filtered;
+    if (d_flat_soa6) *d_flat_soa6 = S.n_flat ? (const float*)S.flat.p : nullptr;
+    if (n_flat) *n_flat = S.n_flat;
+    if (d_intensity) *d_intensity = side;
+    if (d_curvature) *d_curvature = side ? side + S.cap_filtered : nullptr;
+    return IMLS_OK;
+}
+
+int imls_sweep_download(imls_ctx* c, int32_t which, void* records, size_t cap, size_t* n, int32_t* sampled_index) {
+    if (!c) return IMLS_ERR_ARG;
+    if (which < 0 || which > 1) return fail(c, IMLS_ERR_ARG, "sweep_download: which must be 0 or 1");
+    if (!c->sweep.has) return fail(c, IMLS_ERR_STATE, "no sweep processed yet");
+    if (int rc = check_device(c)) return rc;
+    SweepEnv e = sweep_env(c);
+    return sweep_download(e, c->sweep, which, records, cap, n, sampled_index);
+}
+
+int imls_sample_point_cloud_device(imls_ctx* c, const imls_sample_params* p, const float* d_soa6, size_t n,
+                                   const int32_t* d_candidates, size_t n_cand, const float* d_last_soa6, size_t m,
+                                   int32_t* d_sampled_out, size_t* n_sampled, float* d_bin_weights_out,
+                                   uint64_t* nan_normals) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!p || (n_cand > 0 && (!d_soa6 || !d_candidates || !d_sampled_out)))
+        return fail(c, IMLS_ERR_ARG, "bad sample params / pointers");
+    if (p->method == IMLS_SAMPLE_MAJOR_AXIS && m > 0 && !d_last_soa6) return fail(c, IMLS_ERR_ARG, "major_axis needs last_pcl_cloud");
+    if (n >= (1ull << 31) || m >= (1ull << 31) || n_cand >= (1ull << 30)) return fail(c, IMLS_ERR_CAPACITY, "cloud too large");
+    if (int rc = check_device(c)) return rc;
+    SweepEnv e = sweep_env(c);
+    const int rc = sampler_run(e, c->sweep, *p, d_soa6, n, d_candidates, n_cand, d_last_soa6, m, d_sampled_out, n_sampled,
+                               d_bin_weights_out, nan_normals);
+    if (c->timing) {
+        if (rc != IMLS_OK) (void)hipStreamSynchronize(c->stream);
+        harvest_timing(c);
+    }
+    return rc;
+}
+
+void imls_shuffle_positions(uint32_t seed, int32_t size, int32_t k, int32_t* out, size_t* n_out) {
+    std::vector<int> v;
+    shuffle_positions(seed, size, k, v);
+    if (out) std::copy(v.begin(), v.end(), out);
+    if (n_out) *n_out = v.size();
 }
 
 // ---------------------------------------------------------------------------------------------

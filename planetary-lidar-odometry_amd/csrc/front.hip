@@ -191,14 +191,15 @@ T* carve(char*& p, size_t n) {
 
 }  // namespace
 
-int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_host, size_t stride, size_t n_in,
-                  DevBuf& mem, float* out_xyzi, uint32_t* out_index, int32_t* ring_sizes, size_t* n_out,
-                  std::string& err) {
+int front_end_dev(hipStream_t s, const imls_front_params& p, const float* d_soa3, const float* h_soa3, size_t n_in,
+                  DevBuf& mem, FrontDev* fo, int32_t* ring_sizes, size_t* n_out, std::string& err, Xfer* x) {
     *n_out = 0;
+    fo->out = nullptr;
+    fo->idx = nullptr;
     if (p.n_scans != 16 && p.n_scans != 32 && p.n_scans != 64) { err = "scan_line must be 16, 32 or 64"; return IMLS_ERR_ARG; }
     for (int r = 0; r < p.n_scans; ++r) ring_sizes[r] = 0;
     if (n_in == 0) return IMLS_OK;
-    if (n_in > (size_t)0x3fffffff || stride < 3) { err = "bad sweep size / stride"; return IMLS_ERR_ARG; }
+    if (n_in > (size_t)0x3fffffff) { err = "bad sweep size / stride"; return IMLS_ERR_ARG; }
     const int n = (int)n_in;
     size_t cub_bytes = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
@@ -207,7 +208,7 @@ int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_ho
     const size_t need = 3 * nn * 4 + nn + nn * 4 + nn * 4 + 2 * nn * 16 + 4 * nn * 4 + nn * 4 + cub_bytes + 128 * 4 + 16 * 256;
     if (!devbuf_grow(mem, need, need + need / 4)) { err = "hipMalloc (front end)"; return IMLS_ERR_DEVICE; }
     char* q = (char*)mem.p;
-    float* xyz = carve<float>(q, 3 * nn);
+    float* xyz_up = carve<float>(q, 3 * nn);
     unsigned char* ok = carve<unsigned char>(q, nn);
     int* ring = carve<int>(q, nn);
     float* ori_a = carve<float>(q, nn);
@@ -220,14 +221,13 @@ int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_ho
     unsigned* idx = carve<unsigned>(q, nn);
     int* ints = carve<int>(q, 128);
     void* cub_tmp = carve<char>(q, cub_bytes);
-    // the sweep as SoA xyz (host pack: the reference's PointXYZ message records, any stride)
-    std::vector<float> h(3 * nn);
-    for (size_t i = 0; i < nn; ++i) {
-        const float* r = xyz_host + i * stride;
-        h[i] = r[0]; h[nn + i] = r[1]; h[2 * nn + i] = r[2];
-    }
     const unsigned g = (unsigned)((n + kFrontBlock - 1) / kFrontBlock);
-    hipMemcpyAsync(xyz, h.data(), 3 * nn * 4, hipMemcpyHostToDevice, s);
+    const float* xyz = d_soa3;
+    if (!d_soa3) {
+        hipMemcpyAsync(xyz_up, h_soa3, 3 * nn * 4, hipMemcpyHostToDevice, s);
+        xyz = xyz_up;
+        if (x) x->h2d += 3 * nn * 4;
+    }
     k_front_init<<<1, 64, 0, s>>>(ints, n);
     k_front_valid<<<g, kFrontBlock, 0, s>>>(xyz, n, p.is_dense, p.minimum_range, p.maximum_range, ok, ints);
     k_front_ring<<<g, kFrontBlock, 0, s>>>(xyz, n, p.n_scans, ok, ints, ring, ori_a);
@@ -236,13 +236,39 @@ int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_ho
     int hc[64 + 8];
     hipMemcpyAsync(hc, ints, (8 + 64) * 4, hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) { err = "front end failed"; return IMLS_ERR_DEVICE; }
+    if (x) { x->d2h += (8 + 64) * 4; x->syncs += 1; }
     if (hc[1] < 0) return IMLS_OK;                  // nothing survives the filters (the reference indexes an empty cloud)
     size_t m = 0;
     for (int r = 0; r < p.n_scans; ++r) { ring_sizes[r] = hc[8 + r]; m += (size_t)hc[8 + r]; }
     if (m > 0) {
         k_front_gather<<<(unsigned)((m + kFrontBlock - 1) / kFrontBlock), kFrontBlock, 0, s>>>(rec, val2, (int)m, out, idx);
-        hipMemcpyAsync(out_xyzi, out, m * 16, hipMemcpyDeviceToHost, s);
-        if (out_index) hipMemcpyAsync(out_index, idx, m * 4, hipMemcpyDeviceToHost, s);
+        if (hipGetLastError() != hipSuccess) { err = "front end launch failed"; return IMLS_ERR_DEVICE; }
+    }
+    fo->out = out;
+    fo->idx = idx;
+    *n_out = m;
+    return IMLS_OK;
+}
+
+// Host form of imls_scan_front_end: the pack and upload, the device form, the download.
+int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_host, size_t stride, size_t n_in,
+                  DevBuf& mem, float* out_xyzi, uint32_t* out_index, int32_t* ring_sizes, size_t* n_out,
+                  std::string& err) {
+    *n_out = 0;
+    if (n_in > 0 && stride < 3) { err = "bad sweep size / stride"; return IMLS_ERR_ARG; }
+    // the sweep as SoA xyz (host pack: the reference's PointXYZ message records, any stride)
+    const size_t nn = n_in <= (size_t)0x3fffffff ? n_in : 0;
+    std::vector<float> h(3 * nn);
+    for (size_t i = 0; i < nn; ++i) {
+        const float* r = xyz_host + i * stride;
+        h[i] = r[0]; h[nn + i] = r[1]; h[2 * nn + i] = r[2];
+    }
+    FrontDev fo;
+    size_t m = 0;
+    if (int rc = front_end_dev(s, p, nullptr, h.data(), n_in, mem, &fo, ring_sizes, &m, err)) return rc;
+    if (m > 0) {
+        hipMemcpyAsync(out_xyzi, fo.out, m * 16, hipMemcpyDeviceToHost, s);
+        if (out_index) hipMemcpyAsync(out_index, fo.idx, m * 4, hipMemcpyDeviceToHost, s);
         if (hipStreamSynchronize(s) != hipSuccess) { err = "front end failed"; return IMLS_ERR_DEVICE; }
     }
     *n_out = m;

@@ -500,13 +500,41 @@ int launch_ransac_batch(hipStream_t s, const PairDev* tab, const int* n_host, in
                          const RansacParams& rp, int it);
 void ransac_seed_host(uint32_t seed, int st[34]);
 
+// Transfer accounting of a producer call (imls_sweep_info): bytes copied each way and host waits.
+struct Xfer {
+    uint64_t h2d = 0, d2h = 0, syncs = 0;
+};
+
 // scanreg.hip — ring-neighbourhood PCA normals + geometric-features presample (imls_ring_normals_pca)
+// Device form: the cloud as float4 (x, y, z, ·) in HBM (d_pts; null: h_pts is uploaded), the rows
+// left in `mem` (valid until its next use).  Host traffic: the ring offsets and the block table up,
+// 24 bytes of counts down behind one wait.
+struct PcaDev {
+    const unsigned* idx;
+    const float *nrm, *ev, *evec, *feat;
+    const unsigned char* fl;
+    const int* ring_off;               // [n_rings + 1]
+    size_t rows;
+    int n;
+};
+int ring_pca_dev(hipStream_t s, const imls_pca_params& p, const float4* d_pts, const float4* h_pts, const int32_t* sizes,
+                 int n_rings, DevBuf& mem, hipEvent_t* marks, PcaDev* out, uint64_t counters[2], std::string& err,
+                 Xfer* x = nullptr);
 int ring_pca_run(hipStream_t s, const imls_pca_params& p, const float* xyz, size_t stride, const int32_t* sizes,
                  int n_rings, DevBuf& mem, hipEvent_t* marks, uint32_t* index_out, float* normal_out,
                  float* evals_out, float* evecs_out, float* features_out, uint8_t* flags_out, size_t* n_out,
                  uint64_t counters[2], std::string& err);
 
 // front.hip — scan front end: NaN + range filter, ring assignment, relative time (imls_scan_front_end)
+// Device form: the sweep as SoA xyz [3][n] in HBM (d_soa3; null: h_soa3 is uploaded), laserCloud
+// left in `mem` as (x, y, z, intensity) records with the input index of each.  One wait, 288 bytes
+// of counts down.
+struct FrontDev {
+    const float4* out;
+    const unsigned* idx;
+};
+int front_end_dev(hipStream_t s, const imls_front_params& p, const float* d_soa3, const float* h_soa3, size_t n_in,
+                  DevBuf& mem, FrontDev* out, int32_t* ring_sizes, size_t* n_out, std::string& err, Xfer* x = nullptr);
 int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_host, size_t stride, size_t n_in,
                   DevBuf& mem, float* out_xyzi, uint32_t* out_index, int32_t* ring_sizes, size_t* n_out,
                   std::string& err);
@@ -515,6 +543,16 @@ int front_end_run(hipStream_t s, const imls_front_params& p, const float* xyz_ho
 int sample_run(hipStream_t s, const imls_sample_params& p, const float* xyz, const float* nrm, size_t stride, size_t n,
                const int32_t* cand, size_t n_cand, const float* last_xyz, size_t last_stride, size_t m, DevBuf& mem,
                hipEvent_t* marks, int32_t* sampled_out, size_t* n_sampled, float* bin_weights_out, std::string& err);
+// the two sampling kernels on device buffers (sweep.hip reuses them)
+struct FpsJob {
+    int off, n, k, first, out;   // points [off, off+n) of the packed bin clouds; k samples → out[out, out+k); n = 0: no job
+};
+void launch_major_avg(hipStream_t s, const float4* spt, const float4* snr, int ns, const float4* last, int m,
+                      const float4* cbox, float r, float r_proj, int* cnt_out, float* avg_out);
+void launch_fps(hipStream_t s, const float4* pts, const FpsJob* jobs, int n_jobs, double* md, unsigned char* taken, int* out);
+// randomSampling's shuffle (566-582) as positions: std::shuffle permutes positions whatever the
+// contents, so the first min(k, size) entries of the shuffled 0 … size−1 index any bin of that size
+void shuffle_positions(uint32_t seed, int size, int k, std::vector<int>& out);
 // randomSampling (566-582) alone: the first min(max_points, n_cand) entries of the seeded shuffle
 void sample_random_host(const int32_t* cand, size_t n_cand, int32_t max_points, uint32_t shuffle_seed,
                         int32_t* sampled_out, size_t* n_sampled);
@@ -525,9 +563,48 @@ int presample_curvature_run(hipStream_t s, const imls_curvature_params& p, const
                             size_t n_rows, DevBuf& mem, hipEvent_t* marks, float* curvature_out, int32_t* candidates_out,
                             size_t* n_cand, std::string& err);
 
+// the stencil and the candidate compaction on device buffers: curv [n], keep / pos / cand [n_rows]
+void curvature_enqueue(hipStream_t s, const imls_curvature_params& p, const float4* pts, const int* ring_off, int n_rings,
+                       int n, const unsigned* row_index, const unsigned char* row_flags, int n_rows, float* curv,
+                       unsigned* keep, unsigned* pos, int* cand, void* cub_tmp, size_t cub_bytes);
+
 // three_axis.hip — threeAxisSampling (imls_sample_three_axis)
+// keys and per-list top-k on device buffers: ga / gb [nc] float4, gc [nc] float2 (k_ta_keys' inputs),
+// keys [9·nc], out [9·k], nan [1] (zeroed by the caller)
+void three_axis_enqueue(hipStream_t s, const float4* ga, const float4* gb, const float2* gc, int nc, int k,
+                        unsigned long long* keys, int* out, unsigned long long* nan);
 int three_axis_run(hipStream_t s, int points_per_list, const float* xyz, const float* nrm, size_t stride, size_t n,
                    const float* evals, const int32_t* cand, size_t n_cand, DevBuf& mem, hipEvent_t* marks,
                    int32_t* sampled_out, size_t* n_sampled, uint64_t* nan_keys, std::string& err);
+
+// sweep.hip — a raw sweep to pcl_cloud / pcl_surface_cloud in HBM (imls_sweep_process) and the
+// sampler stage on device inputs (imls_sample_point_cloud_device)
+struct SweepSet {                      // one of the two rotating cloud sets
+    DevBuf soa6, side, flat, rows, prev4, cbox;   // side: intensity [n] | curvature [n]
+    size_t n_filtered = 0, n_flat = 0, cap_filtered = 0;
+};
+struct SweepState {
+    SweepSet set[2];
+    int cur = 0;                       // the set holding the last sweep's clouds
+    bool has = false;                  // a sweep ran since creation / reset
+    uint64_t counter = 1;              // scan_registration.cpp:64
+    DevBuf raw, raw3, cand, scratch, rec;
+};
+// timing hook of the caller: a pair of events that will be harvested as `kind`, or false (timing off)
+typedef bool (*SweepMark)(void* owner, int kind, hipEvent_t ev[2]);
+struct SweepEnv {
+    hipStream_t s;
+    DevBuf *front_mem, *pca_mem;
+    SweepMark mark;
+    void* owner;
+    std::string* err;
+};
+int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const float* h_xyz, const float* d_xyz,
+              size_t stride, size_t n, imls_sweep_info* info);
+int sweep_download(SweepEnv& e, SweepState& st, int which, void* records, size_t cap, size_t* n, int32_t* sampled_index);
+int sampler_run(SweepEnv& e, SweepState& st, const imls_sample_params& p, const float* d_soa6, size_t n,
+                const int32_t* d_cand, size_t n_cand, const float* d_last_soa6, size_t m, int32_t* d_sampled,
+                size_t* n_sampled, float* d_weights, uint64_t* nan_normals);
+std::vector<DevBuf*> sweep_buffers(SweepState& st);
 
 }  // namespace imlsgpu

@@ -74,6 +74,17 @@ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
+void curvature_enqueue(hipStream_t s, const imls_curvature_params& p, const float4* pts, const int* ring_off, int n_rings,
+                       int n, const unsigned* row_index, const unsigned char* row_flags, int nr, float* curv,
+                       unsigned* keep, unsigned* pos, int* cand, void* cub_tmp, size_t cub_bytes) {
+    k_curvature<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>(pts, ring_off, n_rings, n, p.window_size, curv);
+    if (nr > 0) {
+        k_curv_flag<<<(nr + kBlock - 1) / kBlock, kBlock, 0, s>>>(curv, row_index, row_flags, nr, p.curvature_threshold, keep);
+        hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, keep, pos, nr, s);
+        k_curv_scatter<<<(nr + kBlock - 1) / kBlock, kBlock, 0, s>>>(keep, pos, nr, cand);
+    }
+}
+
 // Host side of imls_presample_curvature: upload, the stencil, the candidate compaction (the kernels
 // are bracketed by marks[0..1] when non-null), and the D2H of the requested outputs.
 int presample_curvature_run(hipStream_t s, const imls_curvature_params& p, const float* xyz, size_t stride,
@@ -111,16 +122,9 @@ int presample_curvature_run(hipStream_t s, const imls_curvature_params& p, const
     }
     if (!ok) { err = "curvature upload failed"; return IMLS_ERR_DEVICE; }
     if (marks) (void)hipEventRecord(marks[0], s);
-    k_curvature<<<(n + kBlock - 1) / kBlock, kBlock, 0, s>>>((const float4*)(m + o_pts), (const int*)(m + o_off), n_rings, n,
-                                                              p.window_size, (float*)(m + o_cv));
-    if (nr > 0) {
-        k_curv_flag<<<(nr + kBlock - 1) / kBlock, kBlock, 0, s>>>((const float*)(m + o_cv), (const unsigned*)(m + o_ri),
-                                                                  (const unsigned char*)(m + o_rf), nr,
-                                                                  p.curvature_threshold, (unsigned*)(m + o_keep));
-        hipcub::DeviceScan::ExclusiveSum(m + o_cub, cub_bytes, (unsigned*)(m + o_keep), (unsigned*)(m + o_pos), nr, s);
-        k_curv_scatter<<<(nr + kBlock - 1) / kBlock, kBlock, 0, s>>>((const unsigned*)(m + o_keep),
-                                                                     (const unsigned*)(m + o_pos), nr, (int*)(m + o_cand));
-    }
+    curvature_enqueue(s, p, (const float4*)(m + o_pts), (const int*)(m + o_off), n_rings, n, (const unsigned*)(m + o_ri),
+                      (const unsigned char*)(m + o_rf), nr, (float*)(m + o_cv), (unsigned*)(m + o_keep),
+                      (unsigned*)(m + o_pos), (int*)(m + o_cand), m + o_cub, cub_bytes);
     if (marks) (void)hipEventRecord(marks[1], s);
     if (hipGetLastError() != hipSuccess) { err = "curvature launch failed"; return IMLS_ERR_DEVICE; }
     unsigned last_pos = 0, last_keep = 0;

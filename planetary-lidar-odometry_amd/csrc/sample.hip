@@ -107,10 +107,6 @@ __global__ __launch_bounds__(kAvgBlock) void k_major_avg(const float4* __restric
     }
 }
 
-struct FpsJob {
-    int off, n, k, first, out;   // points [off, off+n) of the packed bin clouds; k samples → out[out, out+k)
-};
-
 constexpr int kFpsPPT = 16;            // bin points per thread held in registers (bins ≤ 8192 points)
 
 // block arg-max of (value desc, index asc) — the first maximum of the reference's strict `>` scan
@@ -126,6 +122,7 @@ __global__ __launch_bounds__(kFpsBlock) void k_fps(const float4* __restrict__ pt
     __shared__ double sv[2][kFpsBlock / 64];
     __shared__ int si[2][kFpsBlock / 64];
     const FpsJob J = jobs[blockIdx.x];
+    if (J.n <= 0) return;                               // a bin without a job (block-uniform)
     const float4* P = pts + J.off;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int last = J.first;
@@ -241,6 +238,25 @@ struct HostRng {
 bool grow_buf(DevBuf& b, size_t bytes) { return devbuf_grow(b, bytes, bytes); }
 
 }  // namespace
+
+void launch_major_avg(hipStream_t s, const float4* spt, const float4* snr, int ns, const float4* last, int m,
+                      const float4* cbox, float r, float r_proj, int* cnt_out, float* avg_out) {
+    k_major_avg<<<(ns + kAvgBlock / 64 - 1) / (kAvgBlock / 64), kAvgBlock, 0, s>>>(
+        spt, snr, ns, last, m, cbox, sqrt_threshold(r), sqrt_threshold(r_proj), cnt_out, avg_out);
+}
+
+void launch_fps(hipStream_t s, const float4* pts, const FpsJob* jobs, int n_jobs, double* md, unsigned char* taken, int* out) {
+    k_fps<<<(unsigned)n_jobs, kFpsBlock, 0, s>>>(pts, jobs, md, taken, out);
+}
+
+void shuffle_positions(uint32_t seed, int size, int k, std::vector<int>& out) {
+    std::mt19937 gen(seed);
+    std::vector<int> sh((size_t)std::max(size, 0));
+    for (int i = 0; i < size; ++i) sh[i] = i;
+    std::shuffle(sh.begin(), sh.end(), gen);
+    const int c = std::max(std::min(k, (int)sh.size()), 0);
+    out.insert(out.end(), sh.begin(), sh.begin() + c);
+}
 
 int sample_run(hipStream_t s, const imls_sample_params& p, const float* xyz, const float* nrm, size_t stride, size_t n,
                const int32_t* cand, size_t n_cand, const float* last_xyz, size_t last_stride, size_t m, DevBuf& mem,

@@ -275,12 +275,11 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// Host side of imls_ring_normals_pca: upload, the block table, the PCA kernel (bracketed by
-// marks[0..1] when non-null), the compaction, and the D2H of the requested outputs.
-int ring_pca_run(hipStream_t s, const imls_pca_params& p, const float* xyz, size_t stride, const int32_t* sizes,
-                 int n_rings, DevBuf& mem, hipEvent_t* marks, uint32_t* index_out, float* normal_out,
-                 float* evals_out, float* evecs_out, float* features_out, uint8_t* flags_out, size_t* n_out,
-                 uint64_t counters[2], std::string& err) {
+// Device form of imls_ring_normals_pca: the block table, the PCA kernel (bracketed by marks[0..1]
+// when non-null) and the compaction; the rows stay in `mem`.
+int ring_pca_dev(hipStream_t s, const imls_pca_params& p, const float4* d_pts, const float4* h_pts, const int32_t* sizes,
+                 int n_rings, DevBuf& mem, hipEvent_t* marks, PcaDev* out, uint64_t counters[2], std::string& err,
+                 Xfer* x) {
     std::vector<int> off(n_rings + 1, 0);
     for (int i = 0; i < n_rings; ++i) {
         if (sizes[i] < 0 || sizes[i] > (1 << 20)) { err = "ring size out of range"; return IMLS_ERR_ARG; }
@@ -307,18 +306,23 @@ int ring_pca_run(hipStream_t s, const imls_pca_params& p, const float* xyz, size
            o_cub = align256(o_cnt + 16), total = align256(o_cub + cub_bytes);
     if (!devbuf_grow(mem, total, total)) { err = "hipMalloc (pca scratch)"; return IMLS_ERR_DEVICE; }
     char* m = (char*)mem.p;
-    std::vector<float4> h(nn);
-    for (int k = 0; k < n; ++k) h[k] = make_float4(xyz[k * stride], xyz[k * stride + 1], xyz[k * stride + 2], 0.f);
-    bool ok = hipMemcpyAsync(m + o_pts, h.data(), (size_t)n * 16, hipMemcpyHostToDevice, s) == hipSuccess;
+    bool ok = true;
+    const float4* pts = d_pts;
+    if (!d_pts) {
+        ok = hipMemcpyAsync(m + o_pts, h_pts, (size_t)n * 16, hipMemcpyHostToDevice, s) == hipSuccess;
+        pts = (const float4*)(m + o_pts);
+        if (x) x->h2d += (size_t)n * 16;
+    }
     ok = ok && hipMemcpyAsync(m + o_off, off.data(), (n_rings + 1) * 4ull, hipMemcpyHostToDevice, s) == hipSuccess;
     if (!blocks.empty())
         ok = ok && hipMemcpyAsync(m + o_blk, blocks.data(), blocks.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
+    if (x) x->h2d += (n_rings + 1) * 4ull + blocks.size() * 8;
     ok = ok && hipMemsetAsync(m + o_keep, 0, nn * 4, s) == hipSuccess;
     ok = ok && hipMemsetAsync(m + o_cnt, 0, 16, s) == hipSuccess;
     if (!ok) { err = "pca upload failed"; return IMLS_ERR_DEVICE; }
     if (marks) (void)hipEventRecord(marks[0], s);
     if (!blocks.empty())
-        k_ring_pca<<<(unsigned)blocks.size(), kPcaBlock, 0, s>>>((const float4*)(m + o_pts), (const int*)(m + o_off),
+        k_ring_pca<<<(unsigned)blocks.size(), kPcaBlock, 0, s>>>(pts, (const int*)(m + o_off),
                                                                 n_rings, (const int2*)(m + o_blk), p, (float*)(m + o_outf),
                                                                 (unsigned*)(m + o_keep), (unsigned char*)(m + o_fl), n,
                                                                 (unsigned long long*)(m + o_cnt));
@@ -338,19 +342,47 @@ int ring_pca_run(hipStream_t s, const imls_pca_params& p, const float* xyz, size
     ok = ok && hipMemcpyAsync(cnt, m + o_cnt, 16, hipMemcpyDeviceToHost, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) { err = "pca kernel failed"; return IMLS_ERR_DEVICE; }
-    const size_t r = n > 0 ? (size_t)last_pos + last_keep : 0;
+    if (x) { x->d2h += 24; x->syncs += 1; }
+    out->idx = (const unsigned*)(m + o_idx);
+    out->nrm = (const float*)(m + o_nrm);
+    out->ev = (const float*)(m + o_ev);
+    out->evec = (const float*)(m + o_evec);
+    out->feat = (const float*)(m + o_feat);
+    out->fl = (const unsigned char*)(m + o_flc);
+    out->ring_off = (const int*)(m + o_off);
+    out->rows = n > 0 ? (size_t)last_pos + last_keep : 0;
+    out->n = n;
+    if (counters) { counters[0] = cnt[0]; counters[1] = cnt[1]; }
+    return IMLS_OK;
+}
+
+// Host form of imls_ring_normals_pca: the pack, the device form, and the D2H of the requested outputs.
+int ring_pca_run(hipStream_t s, const imls_pca_params& p, const float* xyz, size_t stride, const int32_t* sizes,
+                 int n_rings, DevBuf& mem, hipEvent_t* marks, uint32_t* index_out, float* normal_out,
+                 float* evals_out, float* evecs_out, float* features_out, uint8_t* flags_out, size_t* n_out,
+                 uint64_t counters[2], std::string& err) {
+    size_t n = 0;
+    for (int i = 0; i < n_rings; ++i) {
+        if (sizes[i] < 0 || sizes[i] > (1 << 20)) { err = "ring size out of range"; return IMLS_ERR_ARG; }
+        n += (size_t)sizes[i];
+    }
+    std::vector<float4> h(std::max<size_t>(n, 1));
+    for (size_t k = 0; k < n; ++k) h[k] = make_float4(xyz[k * stride], xyz[k * stride + 1], xyz[k * stride + 2], 0.f);
+    PcaDev o;
+    if (int rc = ring_pca_dev(s, p, nullptr, h.data(), sizes, n_rings, mem, marks, &o, counters, err)) return rc;
+    const size_t r = o.rows;
     if (r > 0) {
-        if (index_out) ok = ok && hipMemcpyAsync(index_out, m + o_idx, r * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
-        if (normal_out) ok = ok && hipMemcpyAsync(normal_out, m + o_nrm, r * 12, hipMemcpyDeviceToHost, s) == hipSuccess;
-        if (evals_out) ok = ok && hipMemcpyAsync(evals_out, m + o_ev, r * 12, hipMemcpyDeviceToHost, s) == hipSuccess;
-        if (evecs_out) ok = ok && hipMemcpyAsync(evecs_out, m + o_evec, r * 36, hipMemcpyDeviceToHost, s) == hipSuccess;
-        if (features_out) ok = ok && hipMemcpyAsync(features_out, m + o_feat, r * 32, hipMemcpyDeviceToHost, s) == hipSuccess;
-        if (flags_out) ok = ok && hipMemcpyAsync(flags_out, m + o_flc, r, hipMemcpyDeviceToHost, s) == hipSuccess;
+        bool ok = true;
+        if (index_out) ok = ok && hipMemcpyAsync(index_out, o.idx, r * 4, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (normal_out) ok = ok && hipMemcpyAsync(normal_out, o.nrm, r * 12, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (evals_out) ok = ok && hipMemcpyAsync(evals_out, o.ev, r * 12, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (evecs_out) ok = ok && hipMemcpyAsync(evecs_out, o.evec, r * 36, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (features_out) ok = ok && hipMemcpyAsync(features_out, o.feat, r * 32, hipMemcpyDeviceToHost, s) == hipSuccess;
+        if (flags_out) ok = ok && hipMemcpyAsync(flags_out, o.fl, r, hipMemcpyDeviceToHost, s) == hipSuccess;
         ok = ok && hipStreamSynchronize(s) == hipSuccess;
         if (!ok) { err = "pca download failed"; return IMLS_ERR_DEVICE; }
     }
     if (n_out) *n_out = r;
-    if (counters) { counters[0] = cnt[0]; counters[1] = cnt[1]; }
     return IMLS_OK;
 }
 

@@ -152,6 +152,12 @@ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
+void three_axis_enqueue(hipStream_t s, const float4* ga, const float4* gb, const float2* gc, int nc, int k, u64* keys,
+                        int* out, u64* nan) {
+    k_ta_keys<<<(nc + kBlock - 1) / kBlock, kBlock, 0, s>>>(ga, gb, gc, nc, keys, nan);
+    k_ta_select<<<kTaLists, kTaSelBlock, 0, s>>>(keys, nc, k, out);
+}
+
 // Host side of imls_sample_three_axis: the per-candidate gather and upload, the keys, the per-list
 // top-k (the kernels bracketed by marks[0..1] when non-null), the D2H of the 9·k indices.
 int three_axis_run(hipStream_t s, int points_per_list, const float* xyz, const float* nrm, size_t stride, size_t n,
@@ -185,9 +191,8 @@ int three_axis_run(hipStream_t s, int points_per_list, const float* xyz, const f
     ok = ok && hipMemsetAsync(d + o_n, 0, 8, s) == hipSuccess;
     if (!ok) { err = "three_axis upload failed"; return IMLS_ERR_DEVICE; }
     if (marks) (void)hipEventRecord(marks[0], s);
-    k_ta_keys<<<(nc + kBlock - 1) / kBlock, kBlock, 0, s>>>((const float4*)(d + o_a), (const float4*)(d + o_a) + n_cand,
-                                                            (const float2*)(d + o_c), nc, (u64*)(d + o_k), (u64*)(d + o_n));
-    k_ta_select<<<kTaLists, kTaSelBlock, 0, s>>>((const u64*)(d + o_k), nc, k, (int*)(d + o_o));
+    three_axis_enqueue(s, (const float4*)(d + o_a), (const float4*)(d + o_a) + n_cand, (const float2*)(d + o_c), nc, k,
+                       (u64*)(d + o_k), (int*)(d + o_o), (u64*)(d + o_n));
     if (marks) (void)hipEventRecord(marks[1], s);
     if (hipGetLastError() != hipSuccess) { err = "three_axis launch failed"; return IMLS_ERR_DEVICE; }
     unsigned long long nan = 0;

@@ -410,6 +410,65 @@ class ImlsContext:
                                                 int(shuffle_seed) & 0xFFFFFFFF, _ptr(out), C.byref(k)))
         return out[:k.value]
 
+    # -- a raw sweep to the two clouds, in HBM (imls_sweep_process) --------------------------------
+    def sweep_process(self, raw, sweep_params: _abi.ImlsSweepParams, n: Optional[int] = None, stride: int = 3) -> dict:
+        """laserCloudHandler on one raw sweep with every cloud staying on the device.  raw: an
+        (n, 3+) float32 array (uploaded once), or a device pointer (int) to n records of `stride`
+        floats.  Returns imls_sweep_info as a dict; the clouds: sweep_clouds_device / sweep_download."""
+        info = _abi.ImlsSweepInfo()
+        if isinstance(raw, (int, np.integer)):
+            if n is None:
+                raise ValueError("a device sweep needs its point count")
+            self._check(self.lib.imls_sweep_process_device(self.ctx, C.byref(sweep_params), C.c_void_p(int(raw)), stride,
+                                                           int(n), C.byref(info)))
+        else:
+            a = np.ascontiguousarray(raw, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] < 3:
+                raise ValueError("raw must be (n, >=3)")
+            self._check(self.lib.imls_sweep_process(self.ctx, C.byref(sweep_params), _ptr(a), a.shape[1], a.shape[0],
+                                                    C.byref(info)))
+        return info.as_dict()
+
+    def sweep_reset(self):
+        self._check(self.lib.imls_sweep_reset(self.ctx))
+
+    def sweep_clouds_device(self) -> dict:
+        """Device pointers of the last sweep's clouds: filtered / flat (SoA float32[6][n], what
+        set_source_device and map_push_device take) with their counts, intensity and curvature of the
+        filtered cloud.  Valid until the second-next sweep_process on this context."""
+        f, s, i, c = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nf, ns = C.c_size_t(), C.c_size_t()
+        self._check(self.lib.imls_sweep_clouds_device(self.ctx, C.byref(f), C.byref(nf), C.byref(s), C.byref(ns),
+                                                      C.byref(i), C.byref(c)))
+        return dict(filtered=f.value or 0, n_filtered=nf.value, flat=s.value or 0, n_flat=ns.value,
+                    intensity=i.value or 0, curvature=c.value or 0)
+
+    def sweep_download(self, which: int):
+        """The last sweep's pcl_cloud (which=0) or pcl_surface_cloud (which=1) as POINT_DTYPE records;
+        for which=1 also the sampled rows of pcl_cloud: (cloud, rows or None)."""
+        n = C.c_size_t()
+        self._check(self.lib.imls_sweep_download(self.ctx, which, None, 0, C.byref(n), None))
+        cloud = np.zeros(n.value, POINT_DTYPE)
+        rows = np.zeros(n.value, np.int32) if which == 1 else None
+        if n.value:
+            self._check(self.lib.imls_sweep_download(self.ctx, which, _ptr(cloud), n.value, C.byref(n),
+                                                     _ptr(rows) if rows is not None else None))
+        return cloud, rows
+
+    def sample_point_cloud_device(self, soa6_ptr: int, n: int, cand_ptr: int, n_cand: int, last_ptr: int, m: int,
+                                  sampled_ptr: int, sample_params: Optional[_abi.ImlsSampleParams] = None,
+                                  weights_ptr: int = 0):
+        """sample_point_cloud on device inputs (SoA6 cloud, int32 candidates, SoA6 previous cloud)
+        into sampled_ptr (device int32, capacity n_cand + bins).  Returns (rows written, candidates
+        left out for a normal without a histogram bin)."""
+        p = sample_params if sample_params is not None else _abi.default_sample_params()
+        k = C.c_size_t(); nan = C.c_uint64()
+        self._check(self.lib.imls_sample_point_cloud_device(
+            self.ctx, C.byref(p), C.c_void_p(soa6_ptr or None), n, C.c_void_p(cand_ptr or None), n_cand,
+            C.c_void_p(last_ptr or None), m, C.c_void_p(sampled_ptr or None), C.byref(k),
+            C.c_void_p(weights_ptr or None), C.byref(nan)))
+        return k.value, int(nan.value)
+
     def enable_stats(self, on=True):
         """Collect the traversal / neighbour counters (traversal_stats, index_stats' sum_kq / nn_found)."""
         self._check(self.lib.imls_enable_stats(self.ctx, int(on)))
@@ -806,7 +865,9 @@ class LaserOdometry:
 
     def __init__(self, params: Optional[_abi.ImlsParams] = None, device: int = 0, pose_file: Optional[str] = None,
                  output_dir: Optional[str] = None, pipelined: Optional[bool] = None, map_model: str = "raw",
-                 motion_prior: str = "none", rebase_distance: float = 100.0):
+                 motion_prior: str = "none", rebase_distance: float = 100.0, producer=None):
+        self.producer = producer        # a producer.ScanRegistration: process_sweep's raw sweep → device clouds
+        self.last_sweep = None
         if map_model not in ("raw", "compensated"):
             raise ValueError('map_model: "raw" or "compensated"')
         if motion_prior not in ("none", "constant_velocity"):
@@ -873,12 +934,27 @@ class LaserOdometry:
         self.close()
 
     def process(self, filtered_cloud, flat_cloud, timestamp: str = ""):
+        return self._frame(len(flat_cloud), lambda ctx: ctx.set_source(flat_cloud, count=False),
+                           lambda ctx, pose: ctx.map_push(filtered_cloud, pose=pose), timestamp)
+
+    def process_sweep(self, raw, timestamp: str = "", front_params: Optional[_abi.ImlsFrontParams] = None):
+        """process_raw + process with the clouds staying in HBM: the producer given at construction
+        (`producer=`) turns the raw sweep into the two device clouds (process_raw_device), the flat
+        cloud becomes the source (set_source_device) and the filtered cloud joins the map
+        (map_push_device).  Returns what process returns; the sweep's handle is `.last_sweep`."""
+        if self.producer is None:
+            raise ValueError("process_sweep needs a producer: LaserOdometry(..., producer=ScanRegistration(...))")
+        h = self.last_sweep = self.producer.process_raw_device(raw, front_params)
+        return self._frame(h.n_flat, lambda ctx: ctx.set_source_device(h.flat, h.n_flat, count=False),
+                           lambda ctx, pose: ctx.map_push_device(h.filtered, h.n_filtered, pose=pose), timestamp)
+
+    def _frame(self, n_flat: int, set_source, map_push, timestamp: str = ""):
+        """One frame: set_source(ctx) loads the flat cloud, map_push(ctx, pose) pushes the filtered one."""
         # the reference's step timers (laser_odometry.cpp:418-420, 461-475, 660, 677): with output_dir,
         # "Frame time", "1. Preprocessing", "2. Matching and solving in flat points" (registered
         # frames only) and "Total time" are appended to laser_odometry_times.txt
         times = TimesLog(self.output_dir) if self.output_dir else None
         result = None
-        n_flat = len(flat_cloud)
         ctx = self.ctx = self._ctxs[self._cur]
         nxt = self._ctxs[1 - self._cur] if self.pipelined else ctx   # where this frame's scan goes
         pushed = False
@@ -892,7 +968,7 @@ class LaserOdometry:
             # the flat cloud's upload: this path's preprocessing.  Count-less: the registration waits
             # for the filter's count itself, so the host does not also wait here for the count and the
             # kept-index download (one stream synchronisation fewer before the first launch)
-            ctx.set_source(flat_cloud, count=False)
+            set_source(ctx)
         if times:
             times.frame(timestamp)
             times.step("1. Preprocessing")
@@ -904,7 +980,7 @@ class LaserOdometry:
                 result = dict(pose=np.eye(4), iters=0, status=_abi.IMLS_FRAME_TOO_FEW, trace=[])
             elif nxt is not ctx:
                 ctx.register_frame_async()
-                nxt.map_push(filtered_cloud)           # this frame's accumulateTargetCloud, overlapped
+                map_push(nxt, None)                    # this frame's accumulateTargetCloud, overlapped
                 pushed = True
                 pose, iters, status = ctx.register_frame_result()
                 result = dict(pose=pose, iters=iters, status=status, trace=ctx.last_trace)
@@ -927,7 +1003,7 @@ class LaserOdometry:
             if times:
                 times.step("2. Matching and solving in flat points")
         if not pushed:
-            nxt.map_push(filtered_cloud, pose=self.anchor_pose if posed else None)
+            map_push(nxt, self.anchor_pose if posed else None)
             if posed and float(np.linalg.norm(self.anchor_pose[:3, 3])) > self.rebase_distance:
                 nxt.map_rebase(inv_pose(self.anchor_pose))
                 self.anchor_pose = np.eye(4)

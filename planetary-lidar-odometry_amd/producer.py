@@ -12,6 +12,10 @@ GPU through the C ABI.
                                     the map FIFO's input) and pcl_surface_cloud (/laser_cloud_flat,
                                     the registration's source)
 
+  ScanRegistration.process_raw_device(raw)  process_raw with every cloud staying in HBM
+                                    (imls_sweep_process): a DeviceSweep handle with the two clouds as
+                                    device pointers, for LaserOdometry.process_sweep
+
 The sweep comes in ring-concatenated order (`laserCloud`, 1064-1069) with the points per scan
 line.  Sampling follows samplePointCloud's dispatch (761-806): "major_axis" samples its first frame
 with the "normal" method (frame == 1, 783) and every later one against the previous pcl_cloud.
@@ -60,6 +64,7 @@ class ScanRegistration:
         self.shuffle_seed = shuffle_seed
         self.rand_seed = rand_seed
         self.frame = 1                      # scan_registration.cpp:64
+        self._device_frames = 0             # sweeps run through process_raw_device (the context's counter − 1)
         self.last_xyz: Optional[np.ndarray] = None
         self.last_pca: Optional[dict] = None
         self.last_curvature: Optional[np.ndarray] = None   # per laserCloud point (curvature presample)
@@ -98,6 +103,38 @@ class ScanRegistration:
         xyz, inten, _, sizes = self.ctx.scan_front_end(raw_xyz, front_params)
         return self.process(xyz, sizes, inten)
 
+    def sweep_params(self, front_params: Optional[_abi.ImlsFrontParams] = None) -> _abi.ImlsSweepParams:
+        """This frame's imls_sweep_params: the configured chain with the per-frame seeds of
+        sample_params() / _frame_seed()."""
+        sp = _abi.default_sweep_params()
+        if front_params is not None:
+            sp.front = front_params
+        sp.pca = self.pca_params
+        sp.curvature = self.curvature_params
+        if self.normal_params is not None:
+            sp.normal = self.normal_params
+        if self.major_axis_params is not None:
+            sp.major_axis = self.major_axis_params
+        sp.presample_method = _abi.PRESAMPLE_IDS[self.presample_method]
+        sp.sample_method = _abi.SWEEP_SAMPLE_IDS[self.sample_method]
+        sp.points_per_list, sp.max_points = self.points_per_list, self.max_points
+        sp.shuffle_seed = self._frame_seed()
+        sp.rand_seed = (self.rand_seed + self.frame - 1) & 0xFFFFFFFF
+        return sp
+
+    def process_raw_device(self, raw_xyz, front_params: Optional[_abi.ImlsFrontParams] = None, n: Optional[int] = None,
+                           stride: int = 3) -> "DeviceSweep":
+        """process_raw with every cloud staying in HBM (imls_sweep_process): raw_xyz is an (n, 3+)
+        float32 array, or a device pointer with n and stride.  A sequence of calls gives the clouds
+        the same sequence of process_raw calls gives; do not mix the two on one instance (the
+        previous cloud of major_axis lives on the host for one and on the device for the other)."""
+        if self.frame != self._device_frames + 1:
+            raise RuntimeError("process_raw_device: this instance already ran process / process_raw")
+        info = self.ctx.sweep_process(raw_xyz, self.sweep_params(front_params), n, stride)
+        self.frame += 1
+        self._device_frames += 1
+        return DeviceSweep(self.ctx, info, self.ctx.sweep_clouds_device())
+
     def process(self, xyz, ring_sizes, intensity=None):
         """One sweep → (pcl_cloud, pcl_surface_cloud) as POINT_DTYPE arrays (48-byte
         pcl::PointXYZINormal records)."""
@@ -128,6 +165,28 @@ class ScanRegistration:
         self.last_pca = o
         self.last_candidates = cand
         self.last_sampled = sampled
+        return cloud, surface
+
+
+class DeviceSweep:
+    """One sweep's clouds in HBM (ScanRegistration.process_raw_device): device pointers of the
+    filtered and flat clouds (SoA float32[6][n]) with their counts, the filtered cloud's intensity and
+    curvature arrays, and imls_sweep_info as `info`.  Valid until the second-next sweep on the
+    producer's context; download() must be called before the next one."""
+
+    def __init__(self, ctx: ImlsContext, info: dict, clouds: dict):
+        self._ctx = ctx
+        self.info = info
+        self.sweep = info["sweep"]
+        self.filtered, self.n_filtered = clouds["filtered"], clouds["n_filtered"]
+        self.flat, self.n_flat = clouds["flat"], clouds["n_flat"]
+        self.intensity, self.curvature = clouds["intensity"], clouds["curvature"]
+        self.sampled: Optional[np.ndarray] = None
+
+    def download(self):
+        """(pcl_cloud, pcl_surface_cloud) as POINT_DTYPE arrays; the sampled rows land in `.sampled`."""
+        cloud, _ = self._ctx.sweep_download(0)
+        surface, self.sampled = self._ctx.sweep_download(1)
         return cloud, surface
 
 

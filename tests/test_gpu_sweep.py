@@ -1,0 +1,359 @@
+"""GPU: a raw sweep to the two clouds and on to a pose without a host round trip of any cloud
+(imls_sweep_process, imls_sample_point_cloud_device, ScanRegistration.process_raw_device,
+LaserOdometry.process_sweep) against the host-pointer chain (process_raw + process) on a second
+context and against the C++ oracle.  EXACT everywhere: sampled rows, weights as bit patterns, the
+clouds' bytes, poses."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import oracle_ctypes as oc
+from gpu_mem import DevSoa, product_hip
+from planetary_lidar_odometry_amd import _abi, config, imls_icp, producer, synth
+from test_gpu_sample_point_cloud import producer_frames
+from test_sample_point_cloud import two_planes
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with imls_icp.ImlsContext(device=0) as c:
+        yield c
+
+
+@pytest.fixture(scope="module")
+def ctx2():
+    with imls_icp.ImlsContext(device=0) as c:
+        yield c
+
+
+@pytest.fixture(scope="module")
+def scene():
+    return synth.make_scene(3), synth.trajectory(6, 2003)
+
+
+@pytest.fixture(scope="module")
+def raws(scene):
+    """The three raw VLP-16 sweeps of the chain tests."""
+    sc, poses = scene
+    return [synth.raw_sweep(sc, synth.vlp16(), poses[2 + k], 40 + k, start_deg=15.0 * k, n_nan=7, n_close=5)
+            for k in range(3)]
+
+
+@pytest.fixture(scope="module")
+def vlp_frames():
+    return producer_frames("vlp16")
+
+
+def _fp(ns=16, lo=0.5, hi=100.0):
+    p = _abi.default_front_params(ns)
+    p.minimum_range, p.maximum_range = lo, hi
+    return p
+
+
+def d2h(ptr, count, dtype):
+    out = np.zeros(count, dtype)
+    if count:
+        assert product_hip().hipMemcpy(out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), out.nbytes, 2) == 0
+    return out
+
+
+def dev_sample(ctx, xyz, nrm, cand, last, p):
+    """imls_sample_point_cloud_device on uploaded copies of the host arrays → (sampled, weights, left out)."""
+    xyz, nrm = np.asarray(xyz, np.float32), np.asarray(nrm, np.float32)
+    cand = np.ascontiguousarray(cand, np.int32)
+    last = np.zeros((0, 3), np.float32) if last is None else np.asarray(last, np.float32)
+    nb = p.azimuth_bins * p.elevation_bins
+    bufs = []
+
+    def up(a):
+        if a.size == 0:
+            return 0
+        bufs.append(DevSoa(a))
+        return bufs[-1].ptr
+
+    d_soa = up(np.concatenate([xyz.T, nrm.T]))
+    d_cand = up(cand.view(np.float32))
+    d_last = up(np.concatenate([last.T, np.zeros_like(last.T)]))
+    d_out = up(np.zeros(len(cand) + nb + 1, np.float32))
+    d_w = up(np.zeros(nb, np.float32))
+    try:
+        k, left_out = ctx.sample_point_cloud_device(d_soa, len(xyz), d_cand, len(cand), d_last, len(last), d_out, p, d_w)
+        assert k <= len(cand) + nb
+        return d2h(d_out, k, np.int32), d2h(d_w, nb, np.float32), left_out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def check(ctx, xyz, nrm, cand, last, p, left_out=0):
+    so, wo = oc.sample_point_cloud(xyz, nrm, cand, last, p)
+    sh, wh = ctx.sample_point_cloud(xyz, nrm, cand, last, p)
+    sd, wd, lo = dev_sample(ctx, xyz, nrm, cand, last, p)
+    assert np.array_equal(sd, sh) and np.array_equal(sd, so), (len(sd), len(sh), len(so))
+    assert np.array_equal(wd.view(np.uint32), wh.view(np.uint32))
+    assert np.array_equal(wd.view(np.uint32), wo.view(np.uint32))
+    assert lo == left_out
+    return sd
+
+
+# ---- 1. the sampler stage on device inputs ------------------------------------------------------
+
+@pytest.mark.parametrize("method,strategy", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_sampler_two_planes(ctx, method, strategy):
+    xyz, nrm = two_planes(n_each=400)
+    last = np.concatenate([xyz[:400] + [0, 0, 0.2], xyz[400:] + [0.6, 0, 0]]).astype(np.float32)
+    p = _abi.default_sample_params(method)
+    p.sampling_strategy = strategy
+    assert len(check(ctx, xyz, nrm, np.arange(800), last, p)) > 0
+
+
+@pytest.mark.parametrize("method,strategy", [(1, 0), (1, 1), (0, 0), (0, 1)])
+def test_sampler_producer_frames(ctx, vlp_frames, method, strategy):
+    (x0, n0, c0), (x1, n1, c1) = vlp_frames
+    p = _abi.default_sample_params(method)
+    p.sampling_strategy = strategy
+    p.shuffle_seed, p.rand_seed = 11, 7
+    s = check(ctx, x1, n1, c1, x0, p)
+    assert len(s) > 0 and len(set(s.tolist())) == len(s)
+
+
+def test_sampler_edge_cases(ctx):
+    xyz, nrm = two_planes(n_each=50)
+    p = _abi.default_sample_params(1)
+    check(ctx, xyz, nrm, np.arange(0), xyz, p)                   # no candidates
+    check(ctx, xyz, nrm, np.arange(100), np.zeros((0, 3), np.float32), p)   # empty previous cloud: weights NaN
+    check(ctx, xyz, nrm, np.arange(100), xyz + 5.0, p)           # nothing nearby: zero weights
+    p.min_points_per_bin = 1
+    p.max_total_points = 7                                        # k = 0 in some bins: FPS keeps its first index
+    check(ctx, xyz, nrm, np.arange(100), xyz + [0, 0, 0.1], p)
+
+
+@pytest.mark.parametrize("n_each", [19, 20, 100, 101, 200, 201])
+@pytest.mark.parametrize("method", [0, 1])
+def test_sampler_bin_size_thresholds(ctx, method, n_each):
+    """Bins at min_points_per_bin − 1 / min_points_per_bin, and at max_points_per_bin / one above of
+    both methods (normal 100, major_axis 200)."""
+    xyz, nrm = two_planes(n_each=n_each)
+    p = _abi.default_sample_params(method)
+    p.shuffle_seed, p.rand_seed = 3, 9
+    s = check(ctx, xyz, nrm, np.arange(2 * n_each), (xyz + [0, 0.05, 0.1]).astype(np.float32), p)
+    assert (len(s) == 0) == (n_each < 20)
+
+
+@pytest.mark.parametrize("m", [1, 63, 64, 65, 129])
+def test_sampler_previous_cloud_chunk_edges(ctx, m):
+    xyz, nrm = two_planes(n_each=50)
+    last = np.tile(xyz + [0, 0, 0.1], (2, 1)).astype(np.float32)[:m]
+    if m == 65:
+        last[64, 1] = np.nan                                      # a chunk of one point, not finite
+    check(ctx, xyz, nrm, np.arange(100), last, _abi.default_sample_params(1))
+
+
+def test_sampler_leaves_out_a_nan_normal(ctx):
+    xyz, nrm = two_planes(n_each=50)
+    nrm = nrm.copy()
+    nrm[3, 0] = np.nan
+    last = (xyz + [0, 0, 0.1]).astype(np.float32)
+    for method in (0, 1):
+        p = _abi.default_sample_params(method)
+        sd, wd, left_out = dev_sample(ctx, xyz, nrm, np.arange(100), last, p)
+        assert left_out == 1 and 3 not in sd
+        rest = np.delete(np.arange(100), 3)
+        so, wo = oc.sample_point_cloud(xyz, nrm, rest, last, p)
+        assert np.array_equal(sd, so) and np.array_equal(wd.view(np.uint32), wo.view(np.uint32))
+
+
+# ---- 2. the whole chain -------------------------------------------------------------------------
+
+CONFIGS = {
+    "shipped": dict(),
+    "normal": dict(sample_method="normal"),
+    "curvature_three_axis": dict(presample_method="curvature", sample_method="three_axis"),
+    "curvature_random": dict(presample_method="curvature", sample_method="random"),
+    "major_axis_random": dict(major_axis_params="random"),
+}
+
+
+def _producers(ctx, ctx2, name):
+    kw = dict(CONFIGS[name])
+    if kw.get("major_axis_params") == "random":
+        kw["major_axis_params"] = _abi.default_sample_params(_abi.IMLS_SAMPLE_MAJOR_AXIS)
+        kw["major_axis_params"].sampling_strategy = _abi.SAMPLE_RANDOM
+    ctx.sweep_reset()
+    return (producer.ScanRegistration(ctx=ctx, shuffle_seed=4, rand_seed=2, **kw),
+            producer.ScanRegistration(ctx=ctx2, shuffle_seed=4, rand_seed=2, **kw))
+
+
+def _check_transfers(info, raw):
+    """The transfer conditions: control words down, tables up."""
+    assert info["bytes_d2h"] <= 4096, info
+    assert info["bytes_h2d"] - raw.nbytes <= 128 * 1024, info
+    assert info["bytes_h2d"] >= raw.nbytes and 1 <= info["host_syncs"] <= 8
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_chain_matches_the_host_chain(ctx, ctx2, raws, name):
+    dev, host = _producers(ctx, ctx2, name)
+    fp = _fp()
+    last = None
+    for k, raw in enumerate(raws):
+        sp = host.sample_params()
+        h = dev.process_raw_device(raw, fp)
+        cloud, flat = h.download()
+        hcloud, hflat = host.process_raw(raw, fp)
+        assert len(cloud) > 1000 and len(flat) > 100
+        assert cloud.tobytes() == hcloud.tobytes() and flat.tobytes() == hflat.tobytes()
+        assert np.array_equal(h.sampled, host.last_sampled)
+        assert (h.n_filtered, h.n_flat) == (len(hcloud), len(hflat))
+        i = h.info
+        assert (i["sweep"], i["n_input"], i["n_filtered"], i["n_flat"]) == (k + 1, len(raw), len(hcloud), len(hflat))
+        assert i["n_candidates"] == len(host.last_candidates) and i["nan_normals"] == 0 and i["nan_keys"] == 0
+        assert (i["pca_failure"], i["plane_invalid"]) == (host.last_pca["pca_failure"], host.last_pca["plane_invalid"])
+        _check_transfers(i, raw)
+        if name == "shipped":                                       # and the oracle's chain directly
+            ox, oidx, ors = oc.scan_front_end(raw, fp)
+            assert i["n_front"] == len(ox)
+            o = oc.ring_pca(ox[:, :3], ors, _abi.default_pca_params())
+            fxyz = ox[:, :3][o["index"]]
+            assert np.array_equal(cloud["x"], fxyz[:, 0]) and np.array_equal(cloud["normal_z"], o["normal"][:, 2])
+            cand = np.nonzero(o["flags"] & _abi.IMLS_PCA_CANDIDATE)[0]
+            s, _ = oc.sample_point_cloud(fxyz, o["normal"], cand, last, sp)
+            assert np.array_equal(s, h.sampled) and np.array_equal(fxyz[s][:, 1], flat["y"])
+            last = fxyz
+
+
+# ---- 3. buffer rotation -------------------------------------------------------------------------
+
+def _snapshot(h):
+    return (d2h(h.filtered, 6 * h.n_filtered, np.float32).tobytes(), d2h(h.flat, 6 * h.n_flat, np.float32).tobytes(),
+            d2h(h.intensity, h.n_filtered, np.float32).tobytes(), d2h(h.curvature, h.n_filtered, np.float32).tobytes())
+
+
+def test_clouds_survive_the_next_sweep(ctx, ctx2, raws):
+    dev, _ = _producers(ctx, ctx2, "shipped")
+    fp = _fp()
+    h0 = dev.process_raw_device(raws[0], fp)
+    before0 = _snapshot(h0)
+    c0 = h0.download()
+    soa = np.frombuffer(before0[0], np.float32).reshape(6, -1)
+    assert np.array_equal(soa[0], c0[0]["x"]) and np.array_equal(soa[5], c0[0]["normal_z"])
+    assert np.array_equal(np.frombuffer(before0[2], np.float32), c0[0]["intensity"])
+    assert np.array_equal(np.frombuffer(before0[1], np.float32).reshape(6, -1)[1], c0[1]["y"])
+    h1 = dev.process_raw_device(raws[1], fp)
+    before1 = _snapshot(h1)
+    assert _snapshot(h0) == before0                 # sweep k's clouds after sweep k+1 ran
+    assert h1.filtered != h0.filtered
+    dev.process_raw_device(raws[2], fp)
+    assert _snapshot(h1) == before1
+
+
+# ---- 4. input forms and empty sweeps ------------------------------------------------------------
+
+def _sweep_params(ns=16, method=_abi.IMLS_SWEEP_NORMAL):
+    sp = _abi.default_sweep_params()
+    sp.front = _fp(ns) if ns == 16 else _abi.default_front_params(ns)
+    sp.sample_method = method
+    sp.shuffle_seed, sp.rand_seed = 21, 3
+    return sp
+
+
+def _both(ctx):
+    return ctx.sweep_download(0)[0].tobytes(), ctx.sweep_download(1)[0].tobytes(), ctx.sweep_download(1)[1].tobytes()
+
+
+def test_device_input_equals_host_input(ctx, raws):
+    raw = np.ascontiguousarray(np.c_[raws[1], np.arange(len(raws[1]), dtype=np.float32)])   # stride 4
+    sp = _sweep_params()
+    ctx.sweep_reset()
+    ih = ctx.sweep_process(raw, sp)
+    host = _both(ctx)
+    d = DevSoa(raw)
+    try:
+        ctx.sweep_reset()
+        idev = ctx.sweep_process(d.ptr, sp, n=len(raw), stride=4)
+    finally:
+        dev = _both(ctx)
+        d.free()
+    assert dev == host and ih["n_flat"] > 100
+    assert ih["bytes_h2d"] - idev["bytes_h2d"] == raw.nbytes
+    ih.pop("bytes_h2d"), idev.pop("bytes_h2d")
+    assert ih == idev
+
+
+@pytest.mark.parametrize("method", [_abi.IMLS_SWEEP_MAJOR_AXIS, _abi.IMLS_SWEEP_THREE_AXIS, _abi.IMLS_SWEEP_RANDOM])
+def test_empty_sweeps(ctx, raws, method):
+    sp = _sweep_params(method=method)
+    ctx.sweep_reset()
+    for raw in (np.zeros((0, 3), np.float32), np.full((9, 3), 0.01, np.float32), raws[0], np.zeros((0, 3), np.float32)):
+        i = ctx.sweep_process(raw, sp)
+        cl = ctx.sweep_clouds_device()
+        assert (cl["n_filtered"], cl["n_flat"]) == (i["n_filtered"], i["n_flat"])
+        assert (i["n_flat"] > 0) == (len(raw) > 9)
+        assert len(ctx.sweep_download(0)[0]) == i["n_filtered"] and len(ctx.sweep_download(1)[0]) == i["n_flat"]
+    assert i["sweep"] == 4 and i["n_filtered"] == 0
+    ctx.sweep_reset()
+    assert ctx.sweep_process(raws[0], sp)["sweep"] == 1
+
+
+# ---- 5. growth ----------------------------------------------------------------------------------
+
+def test_buffers_grow_and_retire(ctx, ctx2, scene, raws):
+    """VLP-16, HDL-64, VLP-16 on one context: every sweep equals the same sweep on a fresh context,
+    and the major_axis sequence (whose previous cloud changes size) equals the host chain's."""
+    sc, poses = scene
+    big = synth.raw_sweep(sc, synth.hdl64(), poses[3], 41, start_deg=40.0, n_nan=7, n_close=5)
+    seq = [(raws[0], _sweep_params(16)), (big, _sweep_params(64)), (raws[2], _sweep_params(16))]
+    ctx.sweep_reset()
+    got = []
+    for raw, sp in seq:
+        ctx.sweep_process(raw, sp)
+        got.append(_both(ctx))
+    assert len(got[1][0]) > 4 * len(got[0][0])
+    for (raw, sp), g in zip(seq, got):
+        with imls_icp.ImlsContext(device=0) as fresh:
+            fresh.sweep_process(raw, sp)
+            assert _both(fresh) == g
+    dev, host = _producers(ctx, ctx2, "shipped")
+    for raw, sp in seq:
+        cloud, flat = dev.process_raw_device(raw, sp.front).download()
+        hcloud, hflat = host.process_raw(raw, sp.front)
+        assert cloud.tobytes() == hcloud.tobytes() and flat.tobytes() == hflat.tobytes()
+
+
+# ---- 6. odometry --------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("solver", ["ls", "ransac_drpm"])
+@pytest.mark.parametrize("queue,model", [(1, "raw"), (3, "compensated")])
+def test_process_sweep_poses_equal_process(scene, solver, queue, model):
+    sc, _ = scene
+    poses = synth.trajectory(8, 2003)
+    sweeps = [synth.raw_sweep(sc, synth.vlp16(), poses[2 + k], 40 + k, start_deg=15.0 * k, n_nan=7, n_close=5)
+              for k in range(5)]
+    p = config.params_from_config(config.load())
+    p.max_queue_size = queue
+    if solver == "ls":
+        p.solve_method = _abi.IMLS_SOLVE_LS
+    else:
+        assert (p.solve_method, p.ransac_final_method) == (_abi.IMLS_SOLVE_RANSAC, _abi.IMLS_FINAL_DRPM)
+    fp = _fp()
+    with imls_icp.LaserOdometry(p, map_model=model, producer=producer.ScanRegistration(shuffle_seed=4, rand_seed=2)) as a, \
+            imls_icp.LaserOdometry(p, map_model=model) as b:
+        assert a.pipelined == (queue == 1)
+        host = producer.ScanRegistration(shuffle_seed=4, rand_seed=2)
+        try:
+            for k, raw in enumerate(sweeps):
+                ra = a.process_sweep(raw, str(k), fp)
+                rb = b.process(*host.process_raw(raw, fp), str(k))
+                assert (ra is None) == (rb is None) == (k == 0)
+        finally:
+            host.close()
+            a.producer.close()
+        assert len(a.poses) == 4
+        for (ta, pa), (tb, pb) in zip(a.poses, b.poses):
+            assert ta == tb and pa.tobytes() == pb.tobytes()
+        for ra, rb in zip(a.results, b.results):
+            assert ra[1].tobytes() == rb[1].tobytes() and ra[2:] == rb[2:]
+        assert all(r[2] > 0 for r in a.results)
