@@ -644,6 +644,51 @@ int imls_sample_point_cloud_device(imls_ctx* ctx, const imls_sample_params* p, c
  * whatever the contents, so bin[out[i]] is the shuffled bin. */
 void imls_shuffle_positions(uint32_t seed, int32_t size, int32_t k, int32_t* out, size_t* n_out);
 
+/* ---- deskew: per-point motion compensation from relTime --------------------------------- */
+/* What TransformToStart / TransformToEnd do in A-LOAM (laser_odometry.cpp:62-114; switched off in the
+ * reference by `#define DISTORTION 0`, 29-30, the calls commented out, 428 / 459), from the time of
+ * measurement the front end leaves in intensity = ring + scanPeriod·relTime
+ * (scan_registration.cpp:1042-1048).
+ *   motion: row-major 4×4, the sensor at the END of the sweep in the frame of the sensor at its START
+ *     (start ← end; under constant velocity the previous frame's rPose).  R = R(a, θ) with
+ *     v = ½(R32−R23, R13−R31, R21−R12), θ = atan2(‖v‖, (trace R − 1)/2), a = v/‖v‖ ((0, 0, 1) when ‖v‖ = 0).
+ *   per point, in double from the float inputs, evaluated as written (no contraction):
+ *     s = (I − float(int(I))) / scan_period (int truncates; s is not clamped),
+ *     q_start = R(a, s·θ)·p + s·t (Rodrigues: p·cos + (a×p)·sin + a·(a·p)·(1 − cos)),
+ *     IMLS_DESKEW_TO_START: q_start;  IMLS_DESKEW_TO_END: Rᵀ·(q_start − t);
+ *     every coordinate rounded to float once, the intensity kept.  A normal is rotated the same way
+ *     (R(a, s·θ)·n, or Rᵀ·R(a, s·θ)·n) without the translations.
+ *   A row with a non-finite coordinate or intensity is left as it is, bit for bit (its normal too), and
+ *   so is a normal with a non-finite component.  An identity motion launches nothing.
+ *   IMLS_ERR_ARG: a non-finite motion entry, θ ≥ π/2, scan_period ≤ 0 or non-finite, an unknown
+ *   to_frame, a stride below 4 (points) / 3 (normals). */
+typedef enum imls_deskew_frame {
+    IMLS_DESKEW_TO_END = 0,         /* TransformToEnd (laser_odometry.cpp:91-114): the sweep-end frame */
+    IMLS_DESKEW_TO_START = 1        /* TransformToStart (laser_odometry.cpp:62-88): the sweep-start frame */
+} imls_deskew_frame;
+/* Host arrays, in place: xyzi = n records (x, y, z, intensity, …) of stride_floats ≥ 4 floats, normals
+ * (nullable) n records (nx, ny, nz, …) of normal_stride_floats ≥ 3; the other floats of a record are
+ * not touched.  Packs, uploads, runs the kernel of the device form, downloads.
+ * (laser_odometry.cpp:29-30, 62-114, 459; scan_registration.cpp:1042-1048) */
+int imls_deskew(imls_ctx* ctx, const double motion[16], int32_t to_frame, float scan_period, float* xyzi,
+                size_t stride_floats, size_t n, float* normals, size_t normal_stride_floats);
+/* Device arrays, in place, enqueued on the context's stream (nothing is uploaded, the host does not
+ * wait): d_xyzi4 = n float4 records (x, y, z, intensity), d_normals4 (nullable) = n float4 records
+ * (nx, ny, nz, ·), both 16-byte aligned.  With timing on, its events are read by the next call that
+ * synchronises (as imls_knn_device's).
+ * (laser_odometry.cpp:29-30, 62-114, 459; scan_registration.cpp:1042-1048) */
+int imls_deskew_device(imls_ctx* ctx, const double motion[16], int32_t to_frame, float scan_period, float* d_xyzi4,
+                       size_t n, float* d_normals4);
+/* The motion of the sweeps to come: every later imls_sweep_process[_device] on this context deskews
+ * the front end's records with it (scan_period = p->front.scan_period) between the front end and the
+ * ring PCA, on the sweep's stream, as one more launch whose motion is a launch argument — the range
+ * filter, the ring assignment and relTime stay computed on the raw points, as in A-LOAM, and the
+ * normals, the presample, the sampler and both clouds see deskewed points.  Holds until it is set
+ * again; motion = NULL (or the identity) and imls_sweep_reset turn it off, and the sweep is then
+ * launch for launch what it is without this call.
+ * (laser_odometry.cpp:29-30, 62-114, 459; scan_registration.cpp:1042-1048) */
+int imls_sweep_set_motion(imls_ctx* ctx, const double motion[16], int32_t to_frame);
+
 /* ---- nearest-neighbour queries ---------------------------------------------------------- */
 /* Replaces a Nabo::NNSearchD::knn call (imls_icp.cpp:197, 372, 414, 605, 650;
  * laser_odometry.cpp:348) with epsilon = 0 and SORT_RESULTS on the index the context already holds:
@@ -722,7 +767,8 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * 9 = imls_sample_three_axis (keys and per-list top-k), 10 = imls_presample_curvature (stencil and
  * candidate compaction), 11 = the sampler, compaction and cloud-assembly kernels of imls_sweep_process /
  * imls_sample_point_cloud_device (which record 5, 6, 7, 9 and 10 for the kernels they share with
- * the calls above).  enable: 0 off, 1 every kind above (the members of
+ * the calls above), 12 = the deskew kernel (imls_deskew, imls_deskew_device, and the sweep's after
+ * imls_sweep_set_motion).  enable: 0 off, 1 every kind above (the members of
  * an imls_register_frames batch then build their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */

@@ -292,12 +292,40 @@ inline bool solve(int32_t method, imls_params p, const Vec3List& s3, const Vec3L
     to_matrix(D, deltaTrans);
     return true;
 }
+template <class M>
+inline void from_matrix(M& m, double D[16]) { for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) D[r * 4 + c] = m(r, c); }
+inline void from_matrix(const double (&m)[16], double D[16]) { for (int k = 0; k < 16; ++k) D[k] = m[k]; }
+inline void from_matrix(double (&m)[16], double D[16]) { for (int k = 0; k < 16; ++k) D[k] = m[k]; }
 inline imls_params thread_params() {
     // the thread context's current parameters are not readable through the ABI: start from the
     // shipped values; every solver argument the reference passes is applied on top
     return default_ls_params();
 }
 }  // namespace detail
+
+// Stands where TransformToStart / TransformToEnd stand (laser_odometry.cpp:62-114; their calls are
+// commented out at 428 / 459 under `#define DISTORTION 0`, 29-30) — with the per-point interpolation
+// A-LOAM's functions of that name do, which the reference's whole-cloud versions dropped: every point
+// of `cloud` (pcl::PointXYZINormal-shaped: x, y, z, normal_*, intensity = ring + scan_period·relTime,
+// scan_registration.cpp:1042-1048) is moved to the sweep-end frame (to_end) or the sweep-start frame,
+// in place, by imls_deskew on the thread's context.  M: the sensor at the sweep's end in the frame of
+// the sensor at its start (start ← end) — any 4×4 with operator()(r, c), or double[16] row-major.
+template <class CloudPtr, class Mat4>
+void deskewCloudHip(CloudPtr& cloud, Mat4& M, bool to_end, bool transform_normal, float scan_period = 0.1f) {
+    const size_t n = cloud->size();
+    double D[16];
+    detail::from_matrix(M, D);
+    auto& pts = cloud->points;
+    std::vector<float> rec(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        rec[4 * i] = pts[i].x; rec[4 * i + 1] = pts[i].y; rec[4 * i + 2] = pts[i].z; rec[4 * i + 3] = pts[i].intensity;
+    }
+    imls_ctx* ctx = thread_context();
+    float* nrm = (transform_normal && n) ? &pts[0].normal_x : nullptr;
+    detail::check(imls_deskew(ctx, D, to_end ? IMLS_DESKEW_TO_END : IMLS_DESKEW_TO_START, scan_period, rec.data(), 4, n, nrm,
+                              n ? sizeof(pts[0]) / sizeof(float) : 3), ctx);
+    for (size_t i = 0; i < n; ++i) { pts[i].x = rec[4 * i]; pts[i].y = rec[4 * i + 1]; pts[i].z = rec[4 * i + 2]; }
+}
 
 // solver.cpp:74-166 (solver.h:84-90): same arguments.
 template <class Vec3List, class Mat4>

@@ -183,6 +183,10 @@ SWEEP_SAMPLE_IDS = {"major_axis": IMLS_SWEEP_MAJOR_AXIS, "normal": IMLS_SWEEP_NO
                     "three_axis": IMLS_SWEEP_THREE_AXIS, "random": IMLS_SWEEP_RANDOM}
 
 
+IMLS_DESKEW_TO_END, IMLS_DESKEW_TO_START = 0, 1   # imls_deskew_frame
+DESKEW_FRAME_IDS = {"end": IMLS_DESKEW_TO_END, "start": IMLS_DESKEW_TO_START}
+
+
 class ImlsSweepParams(C.Structure):
     """imls_sweep_params (include/imls_gpu.h): the whole producer chain of one imls_sweep_process."""
     _fields_ = [("front", ImlsFrontParams), ("pca", ImlsPcaParams), ("curvature", ImlsCurvatureParams),
@@ -303,6 +307,9 @@ def _bind(lib: C.CDLL, strict: bool = True) -> C.CDLL:
         "imls_sample_point_cloud_device": (C.c_int, [VP, P(ImlsSampleParams), VP, SZ, VP, SZ, VP, SZ, VP, P(SZ), VP,
                                                      P(C.c_uint64)]),
         "imls_shuffle_positions": (None, [C.c_uint32, C.c_int32, C.c_int32, VP, P(SZ)]),
+        "imls_deskew": (C.c_int, [VP, VP, C.c_int32, C.c_float, VP, SZ, SZ, VP, SZ]),
+        "imls_deskew_device": (C.c_int, [VP, VP, C.c_int32, C.c_float, VP, SZ, VP]),
+        "imls_sweep_set_motion": (C.c_int, [VP, VP, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         if not strict and not hasattr(lib, name):
@@ -332,6 +339,7 @@ ABI_SYMBOLS = (
     "imls_default_curvature_params", "imls_presample_curvature", "imls_sample_three_axis", "imls_sample_random",
     "imls_default_sweep_params", "imls_sweep_process", "imls_sweep_process_device", "imls_sweep_reset",
     "imls_sweep_clouds_device", "imls_sweep_download", "imls_sample_point_cloud_device", "imls_shuffle_positions",
+    "imls_deskew", "imls_deskew_device", "imls_sweep_set_motion",
 )
 
 _LIB = None

@@ -139,8 +139,8 @@ void release_retired(int device) {
 }
 }  // namespace imlsgpu
 
-constexpr int kTimingKinds = 12;  // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query,
-                                  // three_axis sampling, curvature presample, sweep sampler / assembly
+constexpr int kTimingKinds = 13;  // projection, index, solve chain, k_knn_wave, k_finish, k_ring_pca, k_major_avg, front end, kNN query,
+                                  // three_axis sampling, curvature presample, sweep sampler / assembly, deskew
 
 // Runtime options of a context (imls_set_option; include/imls_gpu.h documents each): the validated
 // tuning parameters and test hooks.  Nothing is read from the environment.
@@ -223,6 +223,7 @@ struct imls_ctx {
     DevBuf front_mem;                     // imls_scan_front_end scratch
     DevBuf curv_mem;                      // imls_presample_curvature scratch
     DevBuf ta_mem;                        // imls_sample_three_axis scratch
+    DevBuf deskew_mem;                    // imls_deskew staging (records | normals)
     SweepState sweep;                     // imls_sweep_process: the rotating cloud sets, counter, scratch
     // imls_knn / imls_knn_device: buffers of their own (one chunk of ≤ kKnnChunk queries), so a query
     // leaves the loaded source, its order, the correspondences and the neighbour lists alone —
@@ -1292,7 +1293,7 @@ void imls_destroy(imls_ctx* c) {
     if (c->ustream) (void)hipStreamSynchronize(c->ustream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf* bufs[] = {&c->knn_q, &c->knn_perm, &c->knn_scratch, &c->knn_lists, &c->knn_fb, &c->knn_pose, &c->knn_up, &c->knn_out,
-                      &c->cap_mem, &c->front_mem, &c->curv_mem, &c->ta_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
+                      &c->cap_mem, &c->deskew_mem, &c->front_mem, &c->curv_mem, &c->ta_mem, &c->sample_mem, &c->pca_mem, &c->tkept, &c->mten, &c->upload_ten, &c->tvn, &c->rnr, &c->ransac_mem, &c->rng, &c->lkeys, &c->tpt, &c->tnr, &c->mpt, &c->nodes, &c->tscratch, &c->treescratch, &c->permbuf, &c->qperm, &c->fb, &c->prevnn,
                       &c->upload_t, &c->spt, &c->snr, &c->sscratch,
                       &c->upload_s, &c->cs, &c->cd, &c->cn, &c->solve_mem, &c->trace_mem, &c->stats, &c->rows_d, &c->pose_tmp};
     for (DevBuf* b : bufs)
@@ -2721,6 +2722,8 @@ int sweep_process(imls_ctx* c, const imls_sweep_params* p, const float* h_xyz, c
     if (p->sample_method == IMLS_SWEEP_THREE_AXIS && (p->points_per_list < 1 || p->points_per_list > 4096))
         return fail(c, IMLS_ERR_UNSUPPORTED, "three_axis: points_per_list must be in [1, 4096]");
     if (p->sample_method == IMLS_SWEEP_RANDOM && p->max_points < 0) return fail(c, IMLS_ERR_ARG, "random: max_points < 0");
+    if (c->sweep.deskew_on && !(std::isfinite(p->front.scan_period) && p->front.scan_period > 0.f))
+        return fail(c, IMLS_ERR_ARG, "sweep: a motion is set and front.scan_period is not positive");
     if (int rc = check_device(c)) return rc;
     SweepEnv e = sweep_env(c);
     const int rc = sweep_run(e, c->sweep, *p, h_xyz, d_xyz, stride, n, info);
@@ -2749,8 +2752,72 @@ int imls_sweep_reset(imls_ctx* c) {
     c->sweep.counter = 1;
     c->sweep.has = false;
     c->sweep.cur = 0;
+    c->sweep.deskew_on = false;
     for (auto& S : c->sweep.set) S.n_filtered = S.n_flat = S.cap_filtered = 0;
     return IMLS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deskew (deskew.hip): TransformToStart / TransformToEnd from relTime
+// ---------------------------------------------------------------------------------------------
+int imls_sweep_set_motion(imls_ctx* c, const double motion[16], int32_t to_frame) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!motion) {
+        c->sweep.deskew_on = false;
+        return IMLS_OK;
+    }
+    DeskewArg A;
+    bool identity = false;
+    if (int rc = deskew_prepare(motion, to_frame, &A, &identity, c->err)) return rc;
+    c->sweep.deskew_on = !identity;
+    c->sweep.deskew = A;
+    return IMLS_OK;
+}
+
+int imls_deskew_device(imls_ctx* c, const double motion[16], int32_t to_frame, float scan_period, float* d_xyzi4, size_t n,
+                       float* d_normals4) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!motion || (n > 0 && !d_xyzi4)) return fail(c, IMLS_ERR_ARG, "deskew: null motion / records");
+    if (!(std::isfinite(scan_period) && scan_period > 0.f)) return fail(c, IMLS_ERR_ARG, "deskew: scan_period must be positive");
+    if (n > (size_t)0x3fffffff) return fail(c, IMLS_ERR_CAPACITY, "cloud too large");
+    DeskewArg A;
+    bool identity = false;
+    if (int rc = deskew_prepare(motion, to_frame, &A, &identity, c->err)) return rc;
+    if (identity || n == 0) return IMLS_OK;
+    if (int rc = check_device(c)) return rc;
+    int slot;
+    timed_begin(c, 12, slot);
+    deskew_enqueue(c->stream, A, scan_period, (float4*)d_xyzi4, (float4*)d_normals4, n);
+    const bool ok = hipGetLastError() == hipSuccess;
+    timed_end(c, 12, slot);
+    return ok ? IMLS_OK : fail(c, IMLS_ERR_DEVICE, "deskew launch failed");
+}
+
+int imls_deskew(imls_ctx* c, const double motion[16], int32_t to_frame, float scan_period, float* xyzi, size_t stride_floats,
+                size_t n, float* normals, size_t normal_stride_floats) {
+    if (!c) return IMLS_ERR_ARG;
+    if (!motion || (n > 0 && (!xyzi || stride_floats < 4 || (normals && normal_stride_floats < 3))))
+        return fail(c, IMLS_ERR_ARG, "deskew: null motion / records, or stride below 4 (points) / 3 (normals)");
+    if (!(std::isfinite(scan_period) && scan_period > 0.f)) return fail(c, IMLS_ERR_ARG, "deskew: scan_period must be positive");
+    if (n > (size_t)0x3fffffff) return fail(c, IMLS_ERR_CAPACITY, "cloud too large");
+    DeskewArg A;
+    bool identity = false;
+    if (int rc = deskew_prepare(motion, to_frame, &A, &identity, c->err)) return rc;
+    if (identity || n == 0) return IMLS_OK;
+    if (int rc = check_device(c)) return rc;
+    int slot = -1;
+    hipEvent_t marks[2];
+    hipEvent_t* mk = nullptr;
+    if (c->timing && (slot = ev_pair(c)) >= 0) {
+        marks[0] = c->ev[slot];
+        marks[1] = c->ev[slot + 1];
+        mk = marks;
+    }
+    const int rc = deskew_host(c->stream, A, scan_period, xyzi, stride_floats, n, normals, normal_stride_floats, c->deskew_mem,
+                               mk, c->err);
+    if (mk && rc == IMLS_OK) c->ev_pairs[12].push_back({slot, slot + 1});
+    if (c->timing) harvest_timing(c);
+    return rc;
 }
 
 int imls_sweep_clouds_device(imls_ctx* c, const float** d_filtered_soa6, size_t* n_filtered, const float** d_flat_soa6,

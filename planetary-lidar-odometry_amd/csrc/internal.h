@@ -577,6 +577,22 @@ int three_axis_run(hipStream_t s, int points_per_list, const float* xyz, const f
                    const float* evals, const int32_t* cand, size_t n_cand, DevBuf& mem, hipEvent_t* marks,
                    int32_t* sampled_out, size_t* n_sampled, uint64_t* nan_keys, std::string& err);
 
+// deskew.hip — per-point motion compensation from relTime (imls_deskew, imls_sweep_set_motion;
+// TransformToStart / TransformToEnd, laser_odometry.cpp:62-114).  The motion (start ← end) as the
+// kernel takes it, by value like Pose12: rotation axis and angle, translation, Rᵀ (row-major).
+struct DeskewArg {
+    double a[3], theta, t[3], Rt[9];
+    int to_start;                      // IMLS_DESKEW_TO_START: stop at the sweep-start frame
+};
+// The host work of one call: IMLS_ERR_ARG (err set) for a non-finite entry or θ ≥ π/2; *identity
+// when M is exactly I (the caller then launches nothing).
+int deskew_prepare(const double M[16], int to_frame, DeskewArg* out, bool* identity, std::string& err);
+// (x, y, z, intensity) records and, nullable, (nx, ny, nz, ·) records, in place on stream s
+void deskew_enqueue(hipStream_t s, const DeskewArg& A, float scan_period, float4* xyzi, float4* nrm, size_t n);
+// host arrays of any stride: pack, upload, the same launch, download (floats past the 4th / 3rd kept)
+int deskew_host(hipStream_t s, const DeskewArg& A, float scan_period, float* xyzi, size_t stride, size_t n, float* nrm,
+                size_t nstride, DevBuf& mem, hipEvent_t* marks, std::string& err);
+
 // sweep.hip — a raw sweep to pcl_cloud / pcl_surface_cloud in HBM (imls_sweep_process) and the
 // sampler stage on device inputs (imls_sample_point_cloud_device)
 struct SweepSet {                      // one of the two rotating cloud sets
@@ -588,6 +604,8 @@ struct SweepState {
     int cur = 0;                       // the set holding the last sweep's clouds
     bool has = false;                  // a sweep ran since creation / reset
     uint64_t counter = 1;              // scan_registration.cpp:64
+    bool deskew_on = false;            // imls_sweep_set_motion: deskew the front end's records with `deskew`
+    DeskewArg deskew{};
     DevBuf raw, raw3, cand, scratch, rec;
 };
 // timing hook of the caller: a pair of events that will be harvested as `kind`, or false (timing off)

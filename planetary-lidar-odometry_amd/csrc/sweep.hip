@@ -3,7 +3,8 @@
 // (laserCloudHandler, scan_registration.cpp:809-1503).
 //
 // The stages are the existing kernels on device buffers (front.hip, scanreg.hip, presample.hip,
-// three_axis.hip, and sample.hip's k_major_avg / k_fps); this file adds what the host did between them:
+// three_axis.hip, and sample.hip's k_major_avg / k_fps; deskew.hip's kernel after the front end once
+// imls_sweep_set_motion gave a motion); this file adds what the host did between them:
 //   k_sw_soa3        the sweep's records (any stride) → SoA xyz, the front end's input;
 //   k_sw_flag / k_sw_scatter / k_sw_count   geometric-features candidates from the PCA flags, ascending;
 //   k_sw_assemble    pcl_cloud: xyz / intensity / curvature gathered at the PCA's index + the normals,
@@ -632,6 +633,12 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
         if (int rc = front_end_dev(s, p.front, raw3, nullptr, n, *e.front_mem, &fo, ring_sizes, &m, *e.err, &x)) return rc;
     }
     I.n_front = m;
+    // deskew (imls_sweep_set_motion): the front end's records in place, relTime read from their
+    // intensity; everything after this sees the compensated points
+    if (st.deskew_on && m > 0) {
+        Span sp(e, 12);
+        deskew_enqueue(s, st.deskew, p.front.scan_period, const_cast<float4*>(fo.out), nullptr, m);
+    }
 
     // ring PCA
     PcaDev po{};

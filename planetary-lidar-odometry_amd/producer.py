@@ -16,6 +16,10 @@ GPU through the C ABI.
                                     (imls_sweep_process): a DeviceSweep handle with the two clouds as
                                     device pointers, for LaserOdometry.process_sweep
 
+process_raw and process_raw_device take motion= (the sensor at the sweep's end in the frame of the
+sensor at its start): the sweep is then deskewed to its end frame between the front end and the normals
+(imls_deskew / imls_sweep_set_motion; TransformToEnd, laser_odometry.cpp:91-114).
+
 The sweep comes in ring-concatenated order (`laserCloud`, 1064-1069) with the points per scan
 line.  Sampling follows samplePointCloud's dispatch (761-806): "major_axis" samples its first frame
 with the "normal" method (frame == 1, 783) and every later one against the previous pcl_cloud.
@@ -97,10 +101,17 @@ class ScanRegistration:
         sp.rand_seed = (self.rand_seed + self.frame - 1) & 0xFFFFFFFF
         return sp
 
-    def process_raw(self, raw_xyz, front_params: Optional[_abi.ImlsFrontParams] = None):
+    def process_raw(self, raw_xyz, front_params: Optional[_abi.ImlsFrontParams] = None, motion=None):
         """The whole laserCloudHandler on a raw sweep (driver order, (n, 3+) float32): the front end
-        (NaN / range filter, ring assignment, relative time; 862-1069) then process()."""
+        (NaN / range filter, ring assignment, relative time; 862-1069) then process().  motion (4×4:
+        the sensor at the sweep's end in the frame of the sensor at its start): the front end's points
+        are deskewed to the sweep-end frame in between (ImlsContext.deskew; TransformToEnd,
+        laser_odometry.cpp:91-114), with the relative time the front end computed on the raw points."""
         xyz, inten, _, sizes = self.ctx.scan_front_end(raw_xyz, front_params)
+        if motion is not None:
+            fp = front_params if front_params is not None else _abi.default_front_params()
+            rec = self.ctx.deskew(np.c_[xyz, inten], motion, "end", fp.scan_period)
+            xyz, inten = rec[:, :3], rec[:, 3]
         return self.process(xyz, sizes, inten)
 
     def sweep_params(self, front_params: Optional[_abi.ImlsFrontParams] = None) -> _abi.ImlsSweepParams:
@@ -123,13 +134,16 @@ class ScanRegistration:
         return sp
 
     def process_raw_device(self, raw_xyz, front_params: Optional[_abi.ImlsFrontParams] = None, n: Optional[int] = None,
-                           stride: int = 3) -> "DeviceSweep":
+                           stride: int = 3, motion=None) -> "DeviceSweep":
         """process_raw with every cloud staying in HBM (imls_sweep_process): raw_xyz is an (n, 3+)
         float32 array, or a device pointer with n and stride.  A sequence of calls gives the clouds
         the same sequence of process_raw calls gives; do not mix the two on one instance (the
-        previous cloud of major_axis lives on the host for one and on the device for the other)."""
+        previous cloud of major_axis lives on the host for one and on the device for the other).
+        motion: as process_raw's — set on the context for this sweep (sweep_set_motion), so a later
+        call without one is not deskewed."""
         if self.frame != self._device_frames + 1:
             raise RuntimeError("process_raw_device: this instance already ran process / process_raw")
+        self.ctx.sweep_set_motion(motion, "end")
         info = self.ctx.sweep_process(raw_xyz, self.sweep_params(front_params), n, stride)
         self.frame += 1
         self._device_frames += 1

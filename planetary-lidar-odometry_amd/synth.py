@@ -292,6 +292,73 @@ def raw_sweep(scene: Scene, model: ScanModel, pose: np.ndarray, seed: int, start
     return xyz
 
 
+def motion_at(motion: np.ndarray, s: float) -> np.ndarray:
+    """The sensor at fraction s of a sweep whose whole motion is `motion` (4×4, start ← end), in the
+    frame of the sensor at its start: (R(a, s·θ), s·t) with (a, θ) the axis and angle of the motion's
+    rotation — constant angular and linear velocity, the interpolation imls_deskew undoes."""
+    M = np.asarray(motion, dtype=np.float64).reshape(4, 4)
+    R, t = M[:3, :3], M[:3, 3]
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    nv = float(np.linalg.norm(v))
+    theta = math.atan2(nv, (np.trace(R) - 1.0) / 2.0)
+    a = v / nv if nv > 0 else np.array([0.0, 0.0, 1.0])
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    phi = s * theta
+    out = np.eye(4)
+    out[:3, :3] = np.eye(3) * math.cos(phi) + K * math.sin(phi) + np.outer(a, a) * (1.0 - math.cos(phi))
+    out[:3, 3] = s * t
+    return out
+
+
+def _within_reach(scene: Scene, centres: np.ndarray, reach: float) -> Scene:
+    """The sub-scene of the boxes and poles a sensor moving through `centres` can hit within `reach`."""
+    def near(xy, margin):
+        d = np.min(np.hypot(xy[:, None, 0] - centres[None, :, 0], xy[:, None, 1] - centres[None, :, 1]), axis=1)
+        return d < reach + margin
+    boxes, poles = scene.boxes, scene.poles
+    if len(boxes):
+        boxes = boxes[near(boxes[:, :2], np.hypot(boxes[:, 3], boxes[:, 4]))]
+    if len(poles):
+        poles = poles[near(poles[:, :2], poles[:, 2])]
+    return Scene(scene.kind, boxes, poles, scene.terrain, scene.boulders)
+
+
+def raw_sweep_moving(scene: Scene, model: ScanModel, pose_start: np.ndarray, motion: np.ndarray, seed: int,
+                     start_deg: float = 0.0, return_hits: bool = False):
+    """raw_sweep from a sensor that moves while it sweeps: firing column k of n_az (clockwise from
+    `start_deg`, every ring at each step) is cast from pose_start · motion_at(motion, k / n_az), and
+    its returns are given in that column's own sensor frame — what a driver delivers.  (n, 3) float32
+    in firing order; return_hits: also the world point of every return (float64, the return as the
+    column's pose maps it) and the true fraction k / n_az of each."""
+    rng = np.random.default_rng(seed)
+    el = np.radians(model.rings)
+    az = np.radians(np.arange(0.0, 360.0, model.azimuth_step_deg))
+    n_az, n_el = len(az), len(el)
+    az0 = int(round(start_deg / model.azimuth_step_deg)) % n_az
+    pose_start = np.asarray(pose_start, dtype=np.float64)
+    ends = np.stack([pose_start[:3, 3], (pose_start @ motion_at(motion, 1.0))[:3, 3]])
+    sub = _within_reach(scene, ends[:, :2], model.max_range) if scene.kind == "urban" else scene
+    range_noise = rng.normal(0.0, model.range_noise, (n_az, n_el))
+    jitter = rng.normal(0.0, model.xyz_jitter, (n_az, n_el, 3))
+    pts, hits, frac = [], [], []
+    for k in range(n_az):
+        A = az[(az0 - k) % n_az]
+        dl = np.stack([np.cos(el) * math.cos(A), np.cos(el) * math.sin(A), np.sin(el)], 1)
+        T = pose_start @ motion_at(motion, k / n_az)
+        tt, _ = _cast(sub, T[:3, 3], dl @ T[:3, :3].T, model.max_range)
+        ok = np.isfinite(tt) & (tt >= model.min_range) & (tt <= model.max_range)
+        if not ok.any():
+            continue
+        p = dl[ok] * (tt[ok] + range_noise[k][ok])[:, None] + jitter[k][ok]
+        pts.append(p)
+        hits.append(p @ T[:3, :3].T + T[:3, 3])
+        frac.append(np.full(len(p), k / n_az))
+    xyz = np.concatenate(pts).astype(np.float32) if pts else np.zeros((0, 3), np.float32)
+    if return_hits:
+        return xyz, (np.concatenate(hits) if hits else np.zeros((0, 3))), (np.concatenate(frac) if frac else np.zeros(0))
+    return xyz
+
+
 def scan(scene: Scene, model: ScanModel, pose: np.ndarray, seed: int, return_index: bool = False):
     """One sweep from sensor pose (4×4 world←sensor), returned in the SENSOR frame as a
     POINT_DTYPE array in ring-major order (like the reference's scan-ring ordering).  return_index:

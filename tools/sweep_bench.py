@@ -3,15 +3,21 @@
   (a) ScanRegistration.process_raw + LaserOdometry.process — every cloud through host memory;
   (b) LaserOdometry.process_sweep — the clouds stay in HBM (imls_sweep_process).
 
-    python tools/sweep_bench.py [--frames 12] [--warmup 2] [--rounds 3] [--paths ab] [--out FILE.json]
+    python tools/sweep_bench.py [--frames 12] [--warmup 2] [--rounds 3] [--paths ab] [--deskew] [--out FILE.json]
 
 Both paths run in alternated rounds in one process on one GPU, for the LS solver and the shipped
 RANSAC→DRPM.  Per path and solver: the median over the rounds of each round's median ms per frame
 (host clock around calls that end in a stream synchronisation; the warm-up frames of every run are
 dropped) and the round-to-round spread (max − min of the round medians); the producer's share of that
 time; the transfer figures of imls_sweep_info (path (b); path (a) has no such accounting: "not
-measured"); and the device time per frame of timing kinds 5, 6, 7, 9, 10 and 11 from a second pass
+measured"); and the device time per frame of timing kinds 5, 6, 7, 9, 10, 11 and 12 from a second pass
 with the timing events on (that pass gives no ms per frame).  Prints one JSON line.
+--deskew runs the same sweeps with a fixed motion (1 m and 3° per sweep) given to both paths, so the
+deskew kernel runs in every sweep (the stream itself is generated from a sensor at rest in each sweep:
+this times the launch, it does not improve these clouds).  "geometry" (always): one MOVING sweep of the
+sensor model, its filtered cloud (front end → [deskew with the true motion] → ring PCA rows) expressed
+in the sweep-end frame against the generator's world hits — max and median distance in metres, with
+and without the deskew.
 --paths a runs the comparator alone (e.g. against another build of the library through
 IMLS_LIB_PATH)."""
 import argparse
@@ -26,7 +32,8 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-KINDS = {5: "k_ring_pca", 6: "k_major_avg", 7: "front_end", 9: "three_axis", 10: "curvature", 11: "sweep_kernels"}
+KINDS = {5: "k_ring_pca", 6: "k_major_avg", 7: "front_end", 9: "three_axis", 10: "curvature", 11: "sweep_kernels",
+         12: "deskew"}
 
 
 def main():
@@ -36,6 +43,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--paths", default="ab", choices=["ab", "a", "b"])
     ap.add_argument("--model", default="hdl64", choices=["hdl64", "vlp16"])
+    ap.add_argument("--deskew", action="store_true", help="a fixed motion set for every sweep (both paths)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -54,6 +62,24 @@ def main():
     total = a.frames + a.warmup
     traj = synth.trajectory(total + 5, 2001)
     raws = [synth.raw_sweep(scene, sm, traj[5 + k], 3000 + k, start_deg=23.0 * k, n_nan=7, n_close=5) for k in range(total)]
+    import math
+    motion = synth.pose_xyyaw(1.0, 0.05, math.radians(3.0), 0.01, 0.002, 0.004)
+    given = motion if a.deskew else None
+
+    def geometry():
+        """The filtered cloud of one moving sweep against the generator's world hits."""
+        raw, hits, _ = synth.raw_sweep_moving(scene, sm, traj[5], motion, 2999, start_deg=11.0, return_hits=True)
+        end = traj[5] @ motion
+        out = dict(motion="1 m, 3 deg per sweep", raw_points=len(raw))
+        with imls_icp.ImlsContext(device=0) as ctx:
+            xyz, inten, idx, sizes = ctx.scan_front_end(raw, fp)
+            for name in ("as_delivered", "deskewed"):
+                pts = xyz if name == "as_delivered" else ctx.deskew(np.c_[xyz, inten], motion, "end", fp.scan_period)[:, :3]
+                rows = ctx.ring_normals_pca(np.ascontiguousarray(pts), sizes)["index"].astype(np.int64)
+                q = pts[rows].astype(np.float64) @ end[:3, :3].T + end[:3, 3]
+                d = np.linalg.norm(q - hits[idx[rows]], axis=1)
+                out[name] = dict(points=len(rows), max_m=round(float(d.max()), 5), median_m=round(float(np.median(d)), 5))
+        return out
 
     def params(solver):
         p = config.params_from_config(config.load())
@@ -72,9 +98,9 @@ def main():
             if path == "b":
                 plain = sr.process_raw_device
 
-                def timed(raw, front_params=None):
+                def timed(raw, front_params=None, **kw):
                     t = time.perf_counter()
-                    h = plain(raw, front_params)
+                    h = plain(raw, front_params, **kw)
                     prod.append((time.perf_counter() - t) * 1e3)
                     infos.append(h.info)
                     return h
@@ -83,11 +109,11 @@ def main():
             for k, raw in enumerate(raws):
                 t0 = time.perf_counter()
                 if path == "a":
-                    cloud, flat = sr.process_raw(raw, fp)
+                    cloud, flat = sr.process_raw(raw, fp, motion=given)
                     prod.append((time.perf_counter() - t0) * 1e3)
                     lo.process(cloud, flat, str(k))
                 else:
-                    lo.process_sweep(raw, str(k), fp)
+                    lo.process_sweep(raw, str(k), fp, motion=given)
                 ms.append((time.perf_counter() - t0) * 1e3)
             kern = {}
             if timing:
@@ -107,7 +133,7 @@ def main():
     paths = list(a.paths)
     solvers = ("ls", "ransac_drpm")
     res = dict(tool="sweep_bench", sensor=a.model, frames=a.frames, warmup=a.warmup, rounds=a.rounds,
-               raw_points=int(np.mean([len(r) for r in raws])), solvers={})
+               raw_points=int(np.mean([len(r) for r in raws])), deskew=bool(a.deskew), solvers={})
     for solver in solvers:
         for pth in paths:              # warm-up: buffers grown, code objects loaded
             run(pth, solver, False)
@@ -140,6 +166,7 @@ def main():
             out["b_below_a_by_more_than_spread"] = bool(
                 out["a"]["ms_per_frame"] - out["b"]["ms_per_frame"] > max(out["a"]["spread_ms"], out["b"]["spread_ms"]))
         res["solvers"][solver] = out
+    res["geometry"] = geometry()       # after the timed passes: its context and buffers are not part of them
     line = json.dumps(res)
     print(line)
     if a.out:
