@@ -404,7 +404,16 @@ KParams make_kparams(const imls_params& p, const Options& o) {
     k.tv_sigma = p.tensor_sigma;
     k.tv_thr = p.tensor_distance_threshold;
     k.tv_skin = (float)o.tv_skin;
-    k.cos_thr = std::cos(k.angle_thr_deg * M_PI / 180.0);
+    // angle_reject reads "cosine above cos_thr" as "angle below the threshold", which holds for
+    // thresholds in [0°, 180°] only.  The reference compares the angle itself (acos(ca)·180/π > thr,
+    // any double): outside that range the cosine of the nearer end stands in, and the exact branch
+    // of angle_reject, which the cosines within 1e-9 of it and the NaN / out-of-range ones reach,
+    // still compares with the threshold as given.  thr < 0: cos_thr = 1 — every cosine below
+    // 1 − 1e-9 is rejected, the rest by acos (a number in [−1, 1] gives an angle ≥ 0 > thr; NaN and
+    // |ca| > 1 pass).  thr ≥ 180: cos_thr = −1 — every cosine above −1 + 1e-9 passes, the rest by
+    // acos (≤ 180 ≤ thr passes, as do NaNs).  A NaN threshold stays NaN: nothing is rejected.
+    const double thr = k.angle_thr_deg;
+    k.cos_thr = thr < 0.0 ? 1.0 : thr >= 180.0 ? -1.0 : std::cos(thr * M_PI / 180.0);
     return k;
 }
 
