@@ -488,7 +488,12 @@ void imls_default_sample_params(imls_sample_params* p, int32_t method);
  *   candidates[n_cand]: candidate_indices into it; last_xyz[m]: last_pcl_cloud (major_axis only).
  * sampled_out (capacity n_cand + azimuth_bins·elevation_bins) receives sampled_indices in the
  * reference's order; bin_weights_out (nullable, azimuth_bins·elevation_bins floats) the normalised
- * major_axis weights. */
+ * major_axis weights.
+ * One definition of its own, shared with imls_sweep_process (below): a candidate whose normal gives no
+ * histogram bin (a non-finite component, |nz| > 1: the x86 cast of the NaN bin coordinate is INT_MIN)
+ * indexes outside the histogram in the reference; here it is left out of the sampling, so the result is
+ * that of the call without that candidate.  Likewise a bin whose k is negative under the "random"
+ * strategy (all weights NaN, 721-732) contributes no point, as randomSampling's loop (576) takes none. */
 int imls_sample_point_cloud(imls_ctx* ctx, const imls_sample_params* p, const float* xyz, const float* nrm,
                             size_t stride_floats, size_t n, const int32_t* candidates, size_t n_cand,
                             const float* last_xyz, size_t last_stride_floats, size_t m, int32_t* sampled_out,

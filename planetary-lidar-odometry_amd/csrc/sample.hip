@@ -208,6 +208,9 @@ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 int x86_float_to_int(float v) {
     return (v > -2147483904.0f && v < 2147483648.0f) ? static_cast<int>(v) : std::numeric_limits<int>::min();
 }
+int x86_double_to_int(double v) {                      // cvttsd2si
+    return (v > -2147483649.0 && v < 2147483648.0) ? static_cast<int>(v) : std::numeric_limits<int>::min();
+}
 
 // Smallest float t ≥ 0 with sqrt(t) ≥ r in correctly rounded float arithmetic (x86 sqrtss is
 // correctly rounded, as is the device's sqrt_rn), so `sqrt(s) < r` ⇔ `s < t` for every float s ≥ 0.
@@ -230,7 +233,7 @@ struct HostRng {
         std::mt19937 gen(seed + calls++);
         std::vector<int> sh = cand;
         std::shuffle(sh.begin(), sh.end(), gen);
-        const int c = std::min(k, (int)sh.size());
+        const int c = std::max(std::min(k, (int)sh.size()), 0);   // k < 0 (a NaN weight, 732): the loop at 576 takes none
         out.insert(out.end(), sh.begin(), sh.begin() + c);
     }
 };
@@ -272,8 +275,11 @@ int sample_run(hipStream_t s, const imls_sample_params& p, const float* xyz, con
         float elevation = (float)::asin((double)nz);     // ::asin(double)
         if (azimuth < 0) azimuth += 2 * M_PI;
         elevation += M_PI / 2;
-        const int ai = std::min(static_cast<int>(azimuth / (2 * M_PI / AZ)), AZ - 1);
-        const int ei = std::min(static_cast<int>(elevation / (M_PI / EL)), EL - 1);
+        const int ai = std::min(x86_double_to_int(azimuth / (2 * M_PI / AZ)), AZ - 1);
+        const int ei = std::min(x86_double_to_int(elevation / (M_PI / EL)), EL - 1);
+        // a non-finite component or |nz| > 1 gives INT_MIN: no bin.  The reference indexes outside the
+        // histogram there; the candidate is left out, as the device form leaves it out (k_sw_bin)
+        if (ai < 0 || ei < 0) continue;
         hist[(size_t)ai * EL + ei].push_back(idx);
     }
     HostRng rng{p.shuffle_seed};

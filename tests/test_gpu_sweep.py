@@ -153,17 +153,29 @@ def test_sampler_previous_cloud_chunk_edges(ctx, m):
 
 
 def test_sampler_leaves_out_a_nan_normal(ctx):
+    """A candidate whose normal has no histogram bin — a NaN component, nz just above 1 (asin is NaN),
+    nz = −inf — is left out by the device form (and counted) and by the host form: both equal the
+    oracle on the remaining candidates."""
     xyz, nrm = two_planes(n_each=50)
     nrm = nrm.copy()
     nrm[3, 0] = np.nan
+    nrm[7, 2] = np.nextafter(np.float32(1), np.float32(2))
+    nrm[60, 1] = np.nan
+    nrm[99, 2] = -np.inf
+    gone = [3, 7, 60, 99]
     last = (xyz + [0, 0, 0.1]).astype(np.float32)
     for method in (0, 1):
-        p = _abi.default_sample_params(method)
-        sd, wd, left_out = dev_sample(ctx, xyz, nrm, np.arange(100), last, p)
-        assert left_out == 1 and 3 not in sd
-        rest = np.delete(np.arange(100), 3)
-        so, wo = oc.sample_point_cloud(xyz, nrm, rest, last, p)
-        assert np.array_equal(sd, so) and np.array_equal(wd.view(np.uint32), wo.view(np.uint32))
+        for strategy in (0, 1):
+            p = _abi.default_sample_params(method)
+            p.sampling_strategy = strategy
+            p.max_points_per_bin = 30                               # both bins are sampled down
+            sd, wd, left_out = dev_sample(ctx, xyz, nrm, np.arange(100), last, p)
+            assert left_out == len(gone) and not np.isin(gone, sd).any()
+            rest = np.delete(np.arange(100), gone)
+            so, wo = oc.sample_point_cloud(xyz, nrm, rest, last, p)
+            assert len(so) > 0 and np.array_equal(sd, so) and np.array_equal(wd.view(np.uint32), wo.view(np.uint32))
+            sh, wh = ctx.sample_point_cloud(xyz, nrm, np.arange(100), last, p)
+            assert np.array_equal(sh, so) and np.array_equal(wh.view(np.uint32), wo.view(np.uint32))
 
 
 # ---- 2. the whole chain -------------------------------------------------------------------------

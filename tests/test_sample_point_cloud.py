@@ -20,9 +20,14 @@ def two_planes(n_each=300, seed=0):
 
 
 def bin_of(nrm, az_bins=8, el_bins=8):
+    """computeSphericalHistogram's bin (536-564) in the reference's mixed arithmetic: the angles are
+    floats, `azimuth += 2 * M_PI`, `elevation += M_PI / 2` and the two quotients are evaluated in
+    double (and the sums rounded back to float)."""
+    nrm = np.asarray(nrm, np.float32)
     az = np.arctan2(nrm[:, 1], nrm[:, 0]).astype(np.float32)
-    az = np.where(az < 0, az + 2 * np.pi, az)
-    el = np.arcsin(nrm[:, 2].astype(np.float64)) + np.pi / 2
+    az = np.where(az < 0, (az.astype(np.float64) + 2 * np.pi).astype(np.float32), az).astype(np.float64)
+    el = np.arcsin(nrm[:, 2].astype(np.float64)).astype(np.float32)
+    el = (el.astype(np.float64) + np.pi / 2).astype(np.float32).astype(np.float64)
     return (np.minimum((az / (2 * np.pi / az_bins)).astype(int), az_bins - 1) * el_bins
             + np.minimum((el / (np.pi / el_bins)).astype(int), el_bins - 1))
 
