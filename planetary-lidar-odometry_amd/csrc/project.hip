@@ -531,6 +531,28 @@ __device__ __forceinline__ float need_key_ids(const float (&lk)[KL], float r2, i
 #define IMLS_KNN_WAVES 5
 #endif
 #define IMLS_KNN_ATTR __attribute__((amdgpu_waves_per_eu(KL <= 26 ? IMLS_KNN_WAVES : 2)))
+// Wave-wide reductions on the vector pipe (DPP; every lane of the wave active).  dpp_i: lane i takes
+// the value of the lane CTRL names, or `old` where that lane lies outside the row or ROWS excludes
+// lane i's row.  wave_reduce: an inclusive scan along each row of 16 (row_shr 1, 2, 4, 8), then lane
+// 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15) and lane 31 into rows 2 and 3 (row_bcast:31):
+// lane 63 holds the wave's total, which wave_last hands to the scalar side.
+constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShr4 = 0x114, kDppShr8 = 0x118;
+constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143;
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ int dpp_i(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROWS, 0xf, false); }
+struct RedOr { static constexpr int id = 0; __device__ static __forceinline__ int op(int a, int b) { return a | b; } };
+struct RedAdd { static constexpr int id = 0; __device__ static __forceinline__ int op(int a, int b) { return a + b; } };
+template <class R>
+__device__ __forceinline__ int wave_reduce(int v) {
+    v = R::op(v, dpp_i<kDppShr1>(R::id, v));
+    v = R::op(v, dpp_i<kDppShr2>(R::id, v));
+    v = R::op(v, dpp_i<kDppShr4>(R::id, v));
+    v = R::op(v, dpp_i<kDppShr8>(R::id, v));
+    v = R::op(v, dpp_i<kDppBcast15, 0xa>(R::id, v));
+    return R::op(v, dpp_i<kDppBcast31, 0xc>(R::id, v));
+}
+__device__ __forceinline__ int wave_last(int v) { return __builtin_amdgcn_readlane(v, 63); }
+
 // One pass: every lane decides reuse, and the packet walks for the lanes that cannot reuse.  (Round 6
 // tried a compacted second launch for the later iterations and a breadth-first top for the first
 // ones; both measured slower — profiles/r06_compact_rejected/, profiles/r06_bfs_rejected/ — and
@@ -694,6 +716,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
 #ifdef IMLS_DEBUG_WAVE_TRACE
     unsigned dbg_ev = 0, dbg_ins = 0;
     unsigned dbg_sparse = 0, dbg_bcast = 0, dbg_sparse_lanes = 0, dbg_listed_lv = 0;   // … sparse visits where a wanting lane has a listed point in the leaf
+    unsigned dbg_mask_lv = 0;   // sparse visits that built the listed mask (some lane had a new candidate)
     unsigned dbg_seed_steps = 0, dbg_seed_pts = 0;   // seed points where any lane inserted / seed points scanned
 #endif
     // mine: lane k's point k of the leaf (loaded by the caller; zero past the leaf's count)
@@ -736,7 +759,6 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             // keys truncate, so a listed point can lie up to hi(max key) (the insertion loop
             // re-tests d32 < thr_())
             int nin = 0;
-            bool have_inl = !listed;
             if (listed) {
 #pragma unroll
                 for (int k = 0; k < KL; ++k) nin += (unsigned)(pos_(k) - base) < (unsigned)cnt ? 1 : 0;
@@ -752,51 +774,54 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             // (cnt ≥ 1 for every leaf the walk admits — a padded leaf past M has an inverted box — as the
             // broadcast scan's lp[cnt − 1] assumes too; clamped all the same: no undefined shift)
             const unsigned long long inleaf = cnt >= 64 ? ~0ull : (1ull << max(cnt, 0)) - 1ull;
+            // The trip knows nothing of listed points (round 8: no branch in it, and the visited bit
+            // goes by a shift and one and-not): lane q gets its raw candidate mask, and the listed
+            // points are taken out after the loop in vector form, below
             unsigned long long m = want;
             while (m) {
                 const int q = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
-                m &= m - 1;
+                m &= ~(1ull << q);
                 const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xf[0]), q));
                 const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xf[1]), q));
                 const float qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xf[2]), q));
                 const float qb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cb), q));
                 const float ex = mine.x - qx, ey = mine.y - qy, ez = mine.z - qz;
                 const float d32 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-                unsigned long long pm = __ballot(d32 <= qb) & inleaf;
-                if (!have_inl) {
-                    const int nq = __builtin_amdgcn_readlane(nin, q);
-                    if (__popcll(pm) > nq) {
-                        listed_mask();
-                        have_inl = true;
-                    } else {
-                        pm = 0ull;
-                    }
-                }
-                if (pm) {
-                    const unsigned long long inq =
-                        ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(inl >> 32), q) << 32) |
-                        (unsigned)__builtin_amdgcn_readlane((int)(unsigned)inl, q);
-                    pm &= ~inq;
-                }
+                const unsigned long long pm = __ballot(d32 <= qb) & inleaf;
                 cm_lo = imls_amdgcn_writelane((int)(unsigned)pm, q, cm_lo);
                 cm_hi = imls_amdgcn_writelane((int)(unsigned)(pm >> 32), q, cm_hi);
             }
             unsigned long long cm = ((unsigned long long)(unsigned)cm_hi << 32) | (unsigned)cm_lo;
-            while (__ballot(cm != 0ull)) {
-                // every lane takes part in the permutes (lanes without a candidate read lane 0)
-                const int jj = cm ? (int)__builtin_ctzll(cm) : 0;
-                const float px = __shfl(mine.x, jj), py = __shfl(mine.y, jj), pz = __shfl(mine.z, jj);
-                if (cm) {
-                    cm &= cm - 1;
-                    const float ex = px - xf[0], ey = py - xf[1], ez = pz - xf[2];
-                    const float d32 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
-                    if (d32 <= bnd && d32 < thr_()) {
+            // Each lane now owns its mask and its listed count.  A lane with exactly nin candidates
+            // holds only listed points (above), so cm & ~inl is zero there as well: when no lane has
+            // more, every mask is cleared without building inl; else inl is built once, in lockstep,
+            // and taken out of every lane's mask.  (Lanes outside `want` have cm = 0 ≤ nin.)
+            if (listed) {
+                if (__ballot(__popcll(cm) > nin)) {
 #ifdef IMLS_DEBUG_WAVE_TRACE
-                        ++dbg_ins;
+                    ++dbg_mask_lv;
 #endif
-                        ins_(d32, base + jj);
-                        bnd = fmin_nn(r2s, thr_());
-                    }
+                    listed_mask();
+                    cm &= ~inl;
+                } else {
+                    cm = 0ull;
+                }
+            }
+            while (__ballot(cm != 0ull)) {
+                // every lane takes part in the permutes and measures its point (lanes without a
+                // candidate read lane 0's and drop it): one predicate, one divergent region
+                const bool has = cm != 0ull;
+                const int jj = has ? (int)__builtin_ctzll(cm) : 0;
+                const float px = __shfl(mine.x, jj), py = __shfl(mine.y, jj), pz = __shfl(mine.z, jj);
+                cm &= cm - 1ull;   // (0 stays 0)
+                const float ex = px - xf[0], ey = py - xf[1], ez = pz - xf[2];
+                const float d32 = __builtin_fmaf(ex, ex, __builtin_fmaf(ey, ey, ez * ez));
+                if (has & (d32 <= bnd) & (d32 < thr_())) {
+#ifdef IMLS_DEBUG_WAVE_TRACE
+                    ++dbg_ins;
+#endif
+                    ins_(d32, base + jj);
+                    bnd = fmin_nn(r2s, thr_());
                 }
 #ifdef IMLS_DEBUG_WAVE_TRACE
                 ++dbg_ev;
@@ -994,14 +1019,21 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 const float2* cp = reinterpret_cast<const float2*>(t.nodes + 3 * ((size_t)unode << (sw - 1))) + 3 * lane;
                 cb0 = cp[0]; cb1 = cp[1]; cb2 = cp[2];
             }
+            // (a record past the step's last is the last one again, its child masked below; the clamp
+            // is on the 32-bit byte offset — one s_min and a register-offset s_load per record, not
+            // a 64-bit address each)
             float4 R[3 * (kWideMax / 2)];
+            const unsigned lastb = (unsigned)(3 * nrec - 1) * 16u;
 #pragma unroll
             for (int k = 0; k < 3 * (kWideMax / 2); ++k) {
-                const kf4v v = rec[min(k, 3 * nrec - 1)];
+                const kf4v v = *(const kconst_f4*)((const __attribute__((address_space(4))) char*)rec + min((unsigned)k * 16u, lastb));
                 R[k] = make_float4(v.x, v.y, v.z, v.w);
             }
             const float bs = bnd * kBoxSlack;
-            unsigned long long m[kWideMax];
+            // round 8: the lanes keep what they want as one bit per child (no ballot per child), and
+            // the wave's view of it — the wanted children wm, the votes per child — comes from three
+            // DPP reductions on the vector side instead of 8 ballots, 8 popcounts and their selects
+            unsigned wbits = 0u;
             int best = -1;
             float bd = kInfF;
 #pragma unroll
@@ -1009,26 +1041,31 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 const float4 a = R[3 * (k >> 1)], b = R[3 * (k >> 1) + 1], c = R[3 * (k >> 1) + 2];
                 const float d = (k & 1) ? box_d2(xf, b.z, b.w, c.x, c.y, c.z, c.w) : box_d2(xf, a.x, a.y, a.z, a.w, b.x, b.y);
                 const bool w = k < nk && d <= bs;
-                m[k] = __ballot(w);
+                wbits |= w ? (1u << k) : 0u;
                 if (w && d < bd) { bd = d; best = k; }
             }
             // descend into the child most lanes find nearest; stack the other wanted ones so that
-            // they pop in Morton (index) order
-            // (its ballot is carried along by scalar selects: m[cstar] is an indexed register move)
-            int cstar = -1, vbest = 0;
-            unsigned long long mstar = 0ull;
-#pragma unroll
-            for (int k = 0; k < kWideMax; ++k) {
-                const int v = __popcll(__ballot(best == k));
-                if (m[k] && (cstar < 0 || v > vbest)) { cstar = k; vbest = v; mstar = m[k]; }
-            }
+            // they pop in Morton (index) order.  A lane's vote is a one in byte `best` of a 64-bit
+            // word (two halves; a count is ≤ 64, so the bytes never carry); child k's key is
+            // (votes << 3) | (7 − k) in lane k, and the largest key among the wanted children names
+            // the first child with the most votes — the strict `>` of a scan k = 0 … 7 that starts
+            // at the first wanted child
+            const unsigned hot = best < 0 ? 0u : 1u << ((best & 3) * 8);
+            const unsigned wm = (unsigned)wave_last(wave_reduce<RedOr>((int)wbits));
+            const unsigned vlo = (unsigned)wave_last(wave_reduce<RedAdd>((int)(best < 4 ? hot : 0u)));
+            const unsigned vhi = (unsigned)wave_last(wave_reduce<RedAdd>((int)(best < 4 ? 0u : hot)));
+            const unsigned cnt = (unsigned)((((unsigned long long)vhi << 32) | vlo) >> ((lane & 7) * 8)) & 0xffu;
+            // (+ 1: zero, the reductions' identity, stands for "not wanted")
+            unsigned key = (wm >> (lane & 7)) & 1u ? ((cnt << 3) | (unsigned)(7 - (lane & 7))) + 1u : 0u;
+            key = max(key, (unsigned)dpp_i<kDppShr1>(0, (int)key));
+            key = max(key, (unsigned)dpp_i<kDppShr2>(0, (int)key));
+            key = max(key, (unsigned)dpp_i<kDppShr4>(0, (int)key));
+            const unsigned kmax = (unsigned)__builtin_amdgcn_readlane((int)key, 7);   // lanes 0 … 7 hold children 0 … 7
+            const int cstar = kmax == 0u ? -1 : 7 - (int)((kmax - 1u) & 7u);
             // the wanted children but cstar, pushed as the unrolled loop k = 7 … 0 did (child k above
             // every wanted child > k, so they pop in Morton order): child k's slot is sp + the number
             // of pushed children above k.  The divergent section stands alone, before the uniform
             // updates: merged into their if, its join made sp, em, node and pop look divergent
-            unsigned wm = 0u;
-#pragma unroll
-            for (int k = 0; k < kWideMax; ++k) wm |= m[k] ? (1u << k) : 0u;
             const unsigned pm = cstar >= 0 ? wm & ~(1u << cstar) : 0u;
             if (lane < kWideMax && ((pm >> lane) & 1u)) {
                 const int pos = sp + __popc(pm >> (lane + 1));
@@ -1038,7 +1075,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
             }
             if (cstar >= 0) {
                 sp += __popc(pm);
-                em = mstar;
+                em = __ballot((wbits >> cstar) & 1u);
                 node = (node << sw) + cstar;
                 pop = 0;
             }
@@ -1126,7 +1163,7 @@ __device__ __forceinline__ void knn_wave_body(TreeView t, const float4* __restri
                 r[0] = (unsigned)(dbg_t1 - dbg_t0); r[1] = (unsigned)(wall_clock64() - dbg_t1);
                 r[2] = n_leaf; r[3] = n_inner; r[4] = dbg_ev; r[5] = dbg_sparse; r[6] = dbg_bcast;
                 r[7] = __popcll(gl); r[8] = __popcll(wi); r[9] = __popcll(w1); r[10] = __float_as_uint(wmax);
-                r[11] = dbg_sparse_lanes; r[12] = dbg_listed_lv; r[13] = dbg_ins;
+                r[11] = dbg_sparse_lanes; r[12] = dbg_listed_lv | (dbg_mask_lv << 16); r[13] = dbg_ins;
                 r[14] = dbg_seed_steps; r[15] = __builtin_amdgcn_readfirstlane(dbg_seed_pts);
             }
         }
