@@ -35,7 +35,7 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
-// Grow-only device buffers (api.hip).  A buffer being replaced may still be read by work already
+// Grow-only device buffers (api_support.hip).  A buffer being replaced may still be read by work already
 // enqueued on any of the library's streams, and hipFree would wait for the whole device (every
 // context's work in flight, and the host).  So the old buffer is RETIRED instead: an event is
 // recorded on every registered stream of its device that still has work, and the buffer is handed
@@ -339,7 +339,7 @@ int build_batch(hipStream_t s, std::vector<BuildJob>& jobs, DevBuf& scratch, Dev
                 size_t h_table_bytes, std::string& err);
 size_t build_job_bytes();              // bytes per job of the device job table
 
-// index.hip — incremental index of the map FIFO (api.hip map_push / finish_target).  A run = one
+// index.hip — incremental index of the map FIFO (api_map.hip map_push / fifo_build, from api.hip finish_target).  A run = one
 // scan's filtered points Morton-sorted under the FIFO's fixed quantisation: [n] sorted keys, [n]
 // records (xyz, bits(local filtered index)), [n] normals, 256-B aligned parts of one buffer.
 struct FifoRun {
@@ -423,12 +423,7 @@ constexpr int kKnnChunk = 1 << 18;     // queries per launch sequence of imls_kn
 
 constexpr int kStatSkipped = 6;   // nbr_stats slot: lanes whose list was reused without traversal
 int project_blocks(int N);
-// k_finish: the exact stage one lane per query (0) or one quad per query (1: round 6, measured slower —
-// DESIGN §5 round 6; kept for same-box A/B builds, tools/build_full_variant.sh quad -DIMLS_FINISH_QUAD=1)
-#ifndef IMLS_FINISH_QUAD
-#define IMLS_FINISH_QUAD 0
-#endif
-constexpr int kPass1Block = IMLS_FINISH_QUAD ? 64 : 256;   // queries per k_finish block (one pass-1 slab each)
+constexpr int kPass1Block = 256;       // queries per k_finish block (one pass-1 slab each)
 constexpr int kPass1Fallback = 64;     // k_project_lane fallback blocks (one slab each, after the k_finish slabs)
 // Batched projection: one launch per kernel for all `npairs` frames of tab (device), iteration
 // `it` (trace slot), every frame at its own pose / done flag.  n_host: the frames' N (grid shapes).
@@ -607,6 +602,24 @@ struct SweepState {
     bool deskew_on = false;            // imls_sweep_set_motion: deskew the front end's records with `deskew`
     DeskewArg deskew{};
     DevBuf raw, raw3, cand, scratch, rec;
+};
+// Launch kinds of the timing ABI (imls_kernel_timing / imls_timing_intervals, and the Python side):
+// the values are public (include/imls_gpu.h documents each) and do not change.
+enum TimingKind {
+    kTimeProject = 0,     // projection (all its kernels)
+    kTimeIndex = 1,       // index build (all its kernels)
+    kTimeSolve = 2,       // solve chain
+    kTimeKnnWave = 3,     // k_knn_wave alone
+    kTimeFinish = 4,      // k_finish alone
+    kTimeRingPca = 5,     // k_ring_pca
+    kTimeMajorAvg = 6,    // k_major_avg
+    kTimeFrontEnd = 7,    // imls_scan_front_end
+    kTimeKnnQuery = 8,    // imls_knn / imls_knn_device
+    kTimeThreeAxis = 9,   // imls_sample_three_axis
+    kTimeCurvature = 10,  // imls_presample_curvature
+    kTimeSweep = 11,      // sweep sampler / compaction / cloud assembly (recorded by sweep.hip)
+    kTimeDeskew = 12,     // deskew kernel
+    kTimingKinds = 13
 };
 // timing hook of the caller: a pair of events that will be harvested as `kind`, or false (timing off)
 typedef bool (*SweepMark)(void* owner, int kind, hipEvent_t ev[2]);

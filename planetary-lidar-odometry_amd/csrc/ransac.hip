@@ -38,9 +38,6 @@ namespace {
 // large ones (the three passes over the rows dominate).  Exact either way (arg-max and counts).
 constexpr int kHypSmallRows = 4096;
 __host__ __device__ constexpr int hyp_block_of(int cap) { return cap <= kHypSmallRows ? 64 : 256; }
-#ifndef IMLS_QR_WAVE
-#define IMLS_QR_WAVE 1                // a hypothesis' 3×6 QR by one wave, a column per lane (round 6)
-#endif
 constexpr int kHypUnroll = 8;        // FPS passes: rows per thread whose loads are in flight together
 constexpr int kHypGrid = 8192;        // batched hypothesis grid (blocks stride over the running frames' items)
 constexpr int kDrpmSlab = 42;         // 36 noise-mean terms + 6 variance terms per block
@@ -439,148 +436,15 @@ __device__ __forceinline__ void argmax_pair(double& v, int& i, double* sv, int* 
     __syncthreads();
 }
 
-// Eigen ColPivHouseholderQR(R×6).solve(b): basic solution (free unknowns zero).  R is tiny (3);
-// every loop is unrolled with constant indices, the pivot swap is predicated.
-template <int RR>
-__device__ void colpiv_qr_small(double A[RR][6], double b[RR], double x[6]) {
-    constexpr int C = 6, S = RR < C ? RR : C;
-    const double eps = DBL_EPSILON;
-    double nu[C], nd[C], hc[S];
-    int perm[C];
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-        double s = 0;
-#pragma unroll
-        for (int r = 0; r < RR; ++r) s += A[r][k] * A[r][k];
-        nu[k] = nd[k] = sqrt(s);
-        perm[k] = k;
-    }
-    double maxnorm = 0;
-#pragma unroll
-    for (int k = 0; k < C; ++k) maxnorm = fmax(maxnorm, nu[k]);
-    const double thr_helper = (maxnorm * eps) * (maxnorm * eps) / (double)RR;
-    const double ndt = sqrt(eps);
-    int nonzero = S;
-    double maxpivot = 0;
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        int big = k;
-        double bv = nu[k];
-#pragma unroll
-        for (int j = k + 1; j < C; ++j)
-            if (nu[j] > bv) { bv = nu[j]; big = j; }
-        if (nonzero == S && bv * bv < thr_helper * (double)(RR - k)) nonzero = k;
-#pragma unroll
-        for (int j = k + 1; j < C; ++j) {
-            if (j == big) {
-#pragma unroll
-                for (int r = 0; r < RR; ++r) { const double t = A[r][k]; A[r][k] = A[r][j]; A[r][j] = t; }
-                double t = nu[k]; nu[k] = nu[j]; nu[j] = t;
-                t = nd[k]; nd[k] = nd[j]; nd[j] = t;
-                const int ti = perm[k]; perm[k] = perm[j]; perm[j] = ti;
-            }
-        }
-        // makeHouseholderInPlace on column k, rows k..RR−1
-        const double c0 = A[k][k];
-        double tail = 0;
-#pragma unroll
-        for (int r = k + 1; r < RR; ++r) tail += A[r][k] * A[r][k];
-        double tau, beta;
-        if (tail <= DBL_MIN) {
-            tau = 0;
-            beta = c0;
-#pragma unroll
-            for (int r = k + 1; r < RR; ++r) A[r][k] = 0;
-        } else {
-            beta = sqrt(c0 * c0 + tail);
-            if (c0 >= 0) beta = -beta;
-#pragma unroll
-            for (int r = k + 1; r < RR; ++r) A[r][k] = A[r][k] / (c0 - beta);
-            tau = (beta - c0) / beta;
-        }
-        hc[k] = tau;
-        A[k][k] = beta;
-        if (fabs(beta) > maxpivot) maxpivot = fabs(beta);
-        if (tau != 0) {
-#pragma unroll
-            for (int j = k + 1; j < C; ++j) {
-                double tmp = A[k][j];
-#pragma unroll
-                for (int r = k + 1; r < RR; ++r) tmp += A[r][k] * A[r][j];
-                A[k][j] -= tau * tmp;
-#pragma unroll
-                for (int r = k + 1; r < RR; ++r) A[r][j] -= tau * A[r][k] * tmp;
-            }
-        }
-#pragma unroll
-        for (int j = k + 1; j < C; ++j) {
-            if (nu[j] != 0) {
-                double temp = fabs(A[k][j]) / nu[j];
-                temp = (1 + temp) * (1 - temp);
-                temp = temp < 0 ? 0 : temp;
-                const double r2 = nu[j] / nd[j];
-                const double temp2 = temp * r2 * r2;
-                if (temp2 <= ndt) {
-                    double s = 0;
-#pragma unroll
-                    for (int r = k + 1; r < RR; ++r) s += A[r][j] * A[r][j];
-                    nd[j] = nu[j] = sqrt(s);
-                } else {
-                    nu[j] *= sqrt(temp);
-                }
-            }
-        }
-    }
-    const double thr = eps * (double)S;
-    int nz = 0;
-#pragma unroll
-    for (int i = 0; i < S; ++i) nz += (i < nonzero && fabs(A[i][i]) > thr * maxpivot) ? 1 : 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) x[c] = 0;
-    if (nz == 0) return;
-#pragma unroll
-    for (int k = 0; k < S; ++k) {
-        if (k < nz) {
-            const double tau = hc[k];
-            if (RR - k == 1) {
-                b[k] *= 1 - tau;
-            } else if (tau != 0) {
-                double tmp = b[k];
-#pragma unroll
-                for (int r = k + 1; r < RR; ++r) tmp += A[r][k] * b[r];
-                b[k] -= tau * tmp;
-#pragma unroll
-                for (int r = k + 1; r < RR; ++r) b[r] -= tau * A[r][k] * tmp;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = S - 1; i >= 0; --i) {
-        if (i < nz) {
-            double s = b[i];
-#pragma unroll
-            for (int j = i + 1; j < S; ++j)
-                if (j < nz) s -= A[i][j] * b[j];
-            b[i] = s / A[i][i];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        double v = 0;
-#pragma unroll
-        for (int i = 0; i < S; ++i)
-            if (i < nz && perm[i] == c) v = b[i];
-        x[c] = v;
-    }
-}
-
-// colpiv_qr_small<3> by one wave (round 6), lane c < 6 holding column c of A (a[r] = A[r][c]) with its
-// norms and original index: the pivot search reads the six norms, a swap exchanges two lanes' columns,
-// the Householder vector of column k is formed by every lane from lane k's column (the same scalar
-// expressions, so the same bits everywhere), and the update and the norm downdate of the columns
-// right of k run on their own lanes — the one-lane routine's operations, each on the lane that owns
-// the column, so x is its result bit for bit.  The back-substitution (3×3) runs on every lane from the
-// gathered factor.  A hypothesis block's QR 4.8 µs on one lane (tools/ransac_probe.py phase clocks).
+// Eigen ColPivHouseholderQR(3×6).solve(b): basic solution (free unknowns zero), by one wave.  Lane
+// c < 6 holds column c of A (a[r] = A[r][c]) with its norms and original index: the pivot search
+// reads the six norms, a swap exchanges two lanes' columns, the Householder vector of column k is
+// formed by every lane from lane k's column (the same scalar expressions, so the same bits
+// everywhere), and the update and the norm downdate of the columns right of k run on their own
+// lanes — Eigen's operations in Eigen's order, each on the lane that owns the column, so x is the
+// sequential routine's result bit for bit.  The back-substitution (3×3) runs on every lane from the
+// gathered factor.  (The QR on a single lane took 4.8 µs per hypothesis block, tools/ransac_probe.py
+// phase clocks.)
 __device__ void colpiv_qr3_wave(double a[3], double b[3], double x[6]) {
     constexpr int RR = 3, C = 6, S = 3;
     const int lane = threadIdx.x & 63;
@@ -802,7 +666,6 @@ __device__ __forceinline__ void ransac_hyp_one(const double* __restrict__ S, con
     argmax_pair<NT>(bv, bi, sv, si);
     RSTAMP(1);
     const int f2 = bi;
-#if IMLS_QR_WAVE
     if (threadIdx.x < 64) {                   // wave 0: lane c builds column c of the 3×6 system
         const int id[3] = {f0, f1, f2};
         const int lane = threadIdx.x, cc = lane < 6 ? lane : 0;
@@ -833,33 +696,6 @@ __device__ __forceinline__ void ransac_hyp_one(const double* __restrict__ S, con
             for (int k = 0; k < 16; ++k) T[k] = D[k];
         }
     }
-#else
-    if (threadIdx.x == 0) {
-        const int id[3] = {f0, f1, f2};
-        double A[3][6], b[3], x[6], D[16];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int k = id[r];
-            const double s0 = S[3 * k], s1 = S[3 * k + 1], s2 = S[3 * k + 2];
-            const double d0 = Dp[3 * k], d1 = Dp[3 * k + 1], d2 = Dp[3 * k + 2];
-            const double n0 = Np[3 * k], n1 = Np[3 * k + 1], n2 = Np[3 * k + 2];
-            A[r][0] = n2 * s1 - n1 * s2;
-            A[r][1] = n0 * s2 - n2 * s0;
-            A[r][2] = n1 * s0 - n0 * s1;
-            A[r][3] = n0; A[r][4] = n1; A[r][5] = n2;
-            double bb = n0 * (d0 - s0);
-            bb = bb + n1 * (d1 - s1);
-            bb = bb + n2 * (d2 - s2);
-            b[r] = bb;
-        }
-        colpiv_qr_small<3>(A, b, x);
-        RSTAMP(2);
-        delta_from_x(x, D);
-        RSTAMP(3);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) T[k] = D[k];
-    }
-#endif
     __syncthreads();
     int c = 0;
     for (int i = threadIdx.x; i < n; i += NT) {

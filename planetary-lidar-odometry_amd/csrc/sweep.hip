@@ -444,7 +444,7 @@ int sampler_dev(SweepEnv& e, DevBuf& scratch, const imls_sample_params& p, const
 
     std::vector<int> hctl(kCtlBins + NB, 0);
     {
-        Span sp(e, 11);
+        Span sp(e, kTimeSweep);
         if (hipMemsetAsync(ctl, 0, (size_t)(kCtlBins + NB) * 4, s) != hipSuccess) return dev_fail(e, "sampler memset failed");
         if (nc > 0) {
             k_sw_bin<<<blocks_of(nc), kBlock, 0, s>>>(soa6, n, cand, nc, AZ, EL, keys, vals, ctl);
@@ -501,14 +501,14 @@ int sampler_dev(SweepEnv& e, DevBuf& scratch, const imls_sample_params& p, const
     const int have_avg = major && ns > 0 && m > 0;
     if (have_avg) {
         {
-            Span sp(e, 11);
+            Span sp(e, kTimeSweep);
             k_sw_sub<<<(unsigned)NB, kBlock, 0, s>>>(desc, boff, binlist, shuf1, soa6, n, spt, snr);
         }
-        Span sp(e, 6);
+        Span sp(e, kTimeMajorAvg);
         launch_major_avg(s, spt, snr, ns, last4, m, cbox, p.r, p.r_proj, cnt, avg);
     }
     {
-        Span sp(e, 11);
+        Span sp(e, kTimeSweep);
         k_sw_plan<<<1, kBlock, 0, s>>>(p, NB, ctl + kCtlBins, boff, desc, cnt, avg, have_avg, rng, w, kind, kk, out_off, jobs, ctl);
     }
     if (hipGetLastError() != hipSuccess) return dev_fail(e, "sampler launch failed");
@@ -543,7 +543,7 @@ int sampler_dev(SweepEnv& e, DevBuf& scratch, const imls_sample_params& p, const
         if (!ok) return dev_fail(e, "sampler table upload failed");
     }
     {
-        Span sp(e, 11);
+        Span sp(e, kTimeSweep);
         if (p.sampling_strategy == 0 && nc > 0) launch_fps(s, fpts, jobs, NB, md, taken, fres);
         k_sw_out<<<(unsigned)NB, kBlock, 0, s>>>(kind, out_off, boff, binlist, fres, s2off, shuf2, d_sampled);
     }
@@ -579,7 +579,7 @@ int sampler_run(SweepEnv& e, SweepState& st, const imls_sample_params& p, const 
         if (!grow(st.rec, al256(mm * 16) + nch * 32)) return dev_fail(e, "hipMalloc (previous cloud)");
         p4 = (float4*)st.rec.p;
         cbox = (float4*)((char*)st.rec.p + al256(mm * 16));
-        Span sp(e, 11);
+        Span sp(e, kTimeSweep);
         k_sw_p4<<<blocks_of(mm), kBlock, 0, s>>>(d_last_soa6, m, (int)mm, p4);
         enqueue_cbox(s, p4, (int)mm, cbox);
     }
@@ -624,19 +624,19 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
             raw = (const float*)st.raw.p;
         }
         if (!grow(st.raw3, n * 12)) return dev_fail(e, "hipMalloc (sweep SoA)");
-        Span sp(e, 11);
+        Span sp(e, kTimeSweep);
         k_sw_soa3<<<blocks_of(n), kBlock, 0, s>>>(raw, stride, (int)n, (float*)st.raw3.p);
         raw3 = (const float*)st.raw3.p;
     }
     {
-        Span sp(e, 7);
+        Span sp(e, kTimeFrontEnd);
         if (int rc = front_end_dev(s, p.front, raw3, nullptr, n, *e.front_mem, &fo, ring_sizes, &m, *e.err, &x)) return rc;
     }
     I.n_front = m;
     // deskew (imls_sweep_set_motion): the front end's records in place, relTime read from their
     // intensity; everything after this sees the compensated points
     if (st.deskew_on && m > 0) {
-        Span sp(e, 12);
+        Span sp(e, kTimeDeskew);
         deskew_enqueue(s, st.deskew, p.front.scan_period, const_cast<float4*>(fo.out), nullptr, m);
     }
 
@@ -645,7 +645,7 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
     uint64_t pc[2] = {0, 0};
     if (m > 0) {
         hipEvent_t mk[2];
-        const bool timed = e.mark && e.mark(e.owner, 5, mk);
+        const bool timed = e.mark && e.mark(e.owner, kTimeRingPca, mk);
         if (int rc = ring_pca_dev(s, p.pca, fo.out, nullptr, ring_sizes, p.front.n_scans, *e.pca_mem, timed ? mk : nullptr, &po,
                                   pc, *e.err, &x))
             return rc;
@@ -678,12 +678,12 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
         void* cub_tmp = carve<char>(q, cub_bytes);
         const bool curvature = p.presample_method == IMLS_PRESAMPLE_CURVATURE;
         if (curvature) {
-            Span sp(e, 10);
+            Span sp(e, kTimeCurvature);
             curvature_enqueue(s, p.curvature, fo.out, po.ring_off, p.front.n_scans, (int)m, po.idx, po.fl, rows, curv, keep, pos,
                               cand, cub_tmp, cub_bytes);
         }
         {
-            Span sp(e, 11);
+            Span sp(e, kTimeSweep);
             if (!curvature) {
                 k_sw_flag<<<blocks_of(R), kBlock, 0, s>>>(po.fl, rows, keep);
                 hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, keep, pos, rows, s);
@@ -724,10 +724,10 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
                 d_nan = carve<unsigned long long>(t, 1);
                 if (hipMemsetAsync(d_nan, 0, 8, s) != hipSuccess) return dev_fail(e, "three_axis memset failed");
                 {
-                    Span sp(e, 11);
+                    Span sp(e, kTimeSweep);
                     k_sw_ta_gather<<<blocks_of(C), kBlock, 0, s>>>((const float*)S.soa6.p, rows, po.ev, cand, n_cand, ga, gb, gc);
                 }
-                Span sp(e, 9);
+                Span sp(e, kTimeThreeAxis);
                 three_axis_enqueue(s, ga, gb, gc, n_cand, k, keys, (int*)S.rows.p, d_nan);
             }
         } else if (p.sample_method == IMLS_SWEEP_RANDOM) {
@@ -739,7 +739,7 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
                 if (hipMemcpyAsync(st.scratch.p, hp.data(), (size_t)n_flat * 4, hipMemcpyHostToDevice, s) != hipSuccess)
                     return dev_fail(e, "random table upload failed");
                 x.h2d += (size_t)n_flat * 4;
-                Span sp(e, 11);
+                Span sp(e, kTimeSweep);
                 k_sw_pick<<<blocks_of(n_flat), kBlock, 0, s>>>(cand, (const int*)st.scratch.p, n_flat, (int*)S.rows.p);
             }
         } else {
@@ -761,7 +761,7 @@ int sweep_run(SweepEnv& e, SweepState& st, const imls_sweep_params& p, const flo
         }
         if (cap_flat > 0) {
             if (!grow(S.flat, (size_t)cap_flat * 24)) return dev_fail(e, "hipMalloc (flat cloud)");
-            Span sp(e, 11);
+            Span sp(e, kTimeSweep);
             k_sw_gather_flat<<<blocks_of(cap_flat), kBlock, 0, s>>>((const float*)S.soa6.p, rows, (const int*)S.rows.p, d_nout,
                                                                     n_flat, (float*)S.flat.p);
         }

@@ -1,4 +1,4 @@
-"""Buffer growth while other work is in flight (api.hip devbuf_grow): a replaced device buffer is
+"""Buffer growth while other work is in flight (api_support.hip devbuf_grow): a replaced device buffer is
 retired behind an event on every library stream that still had work — never freed under a pending
 kernel, and no device-wide synchronisation.  Results must be bit-equal to the same registrations on
 fresh contexts (nothing grown, nothing in flight beside them)."""
