@@ -222,6 +222,80 @@ int imls_set_source_device(imls_ctx* ctx, const float* d_soa6, size_t n, size_t*
  * and imls_map_push_device (and to the owned upload buffers of the host-pointer forms). */
 int imls_set_defer(imls_ctx* ctx, int on);
 
+/* ---- pose covariance and degeneracy report ---------------------------------------------- */
+/* What the last successful solve of a context knew about its own pose (the reference declares the
+ * output and never fills it: IMLSICPMatcher::Match does covariance.setIdentity(), imls_icp.cpp:797-811;
+ * the six DRPM probabilities are printed and dropped, solver.cpp:555-560).
+ *
+ * Parameter order: ξ = (ωx, ωy, ωz, tx, ty, tz), the solver's x (solver.cpp:89-107, 140-163): an
+ * increment applied on the left, in the target / map frame: rPose ← Δ(x)·rPose.
+ *
+ * Rows: with (a_i, b_i) one row of the point-to-plane system (solver.cpp:95-103) and w_i its weight,
+ * the sums run over the rows of the FINAL 6×6 system of that solve:
+ *   LS (the loop method, imls_solve, imls_solve_correspondences): the ranks ⌊t·N⌋ … min(⌊(1−t)·N⌋, N−1)
+ *     of the order (|r₁|, row), r₁ the residual under the first solve, t = ls_threshold; w = 1;
+ *   Weighted LS: every valid row, the caller's weights (else 1);
+ *   RANSAC → LS: the same trim with ransac_ls_threshold over the inliers of the best hypothesis, w = 1;
+ *   RANSAC → Weighted LS / DRPM: every inlier, w_i / Σw (solver.cpp:334-364);
+ *   DRPM on caller rows: every row, the caller's weights.
+ *
+ * What it is: the formal covariance of that one linear solve — the linearisation at the pose BEFORE
+ * the iteration's Δ, over the rows the solve used.  It mixes radians and metres, knows nothing of
+ * wrong correspondences, and is optimistic under trimming and Huber weights: with 500 well-spread
+ * rows and Gaussian noise on b, the ratio of sample variance to reported variance per diagonal was
+ * 0.97–1.05 without trim, 1.02–1.32 at ls_threshold 0.02 and 1.2–1.75 at 0.1 (400 trials, CPU).  No
+ * correction is applied.
+ *
+ * A registration reports the iteration whose Δ produced the returned pose.  The pass runs once, behind
+ * the loop, over the rows still on the device: a frame that ran no iteration, or that ended TOO_FEW /
+ * SOLVE_FAILED (before any solve succeeded, or after one — that iteration's projection has then
+ * replaced the rows of the last good solve), reports flags = 0 and zeros elsewhere. */
+#define IMLS_INFO_RANK_RELTOL 1e-12   /* rank = #{k : λ_k > IMLS_INFO_RANK_RELTOL · λ_5} */
+enum {
+    IMLS_INFO_VALID = 1,
+    IMLS_INFO_RANK_DEFICIENT = 2,     /* rank < 6 */
+    IMLS_INFO_NO_DOF = 4,             /* n_rows ≤ rank: sigma2 and covariance are zero */
+    IMLS_INFO_DRPM_RAN = 8,
+    IMLS_INFO_DRPM_DEGENERATE = 16    /* min p < drpm_threshold: the SNR-weighted branch was taken */
+};
+/* (a struct tag, not a typedef: the call below carries the same name, so C and C++ callers write
+ * `struct imls_pose_info`) */
+struct imls_pose_info {
+    double hessian[36];               /* Σ w a aᵀ, row-major */
+    double gradient[6];               /* Σ w a b */
+    double x[6];                      /* the vector the solve turned into Δ (DRPM's degenerate branch:
+                                         U·diag(p/λ)·Uᵀg) */
+    double btb;                       /* Σ w b² */
+    double rss;                       /* Σ w (a·x − b)², summed row by row */
+    double weight_sum;                /* Σ w */
+    uint64_t n_rows;
+    double eigenvalues[6];            /* of hessian, ascending */
+    double eigenvectors[36];          /* vector k at [6k … 6k+5]; the largest-magnitude component of
+                                         each is positive (the first such component on a tie) */
+    double sigma2;                    /* rss / (n_rows − rank) */
+    double covariance[36];            /* sigma2 · Σ_{λ_k kept} u_k u_kᵀ / λ_k (pseudo-inverse over the
+                                         observable subspace), row-major */
+    double drpm_probability[6];       /* the values solver.cpp:555-560 prints, in eigenvalue order of
+                                         the DRPM solve; zero unless DRPM ran */
+    int32_t rank;
+    int32_t iteration;                /* index into the trace (0 for a stand-alone solve) */
+    int32_t status;                   /* imls_frame_status of the frame / solve */
+    int32_t solve_method;             /* imls_solve_method */
+    int32_t final_method;             /* imls_final_method (RANSAC), else 0 */
+    uint32_t flags;                   /* IMLS_INFO_* */
+    int32_t _reserved[2];
+};
+/* Sticky, default off.  While off every launch sequence and every result is what it is without this
+ * feature.  While on, two more launches follow each solve sequence on the same stream — the loop of
+ * imls_register_frame[_async], each member's frame of imls_register_frames[_async] (every member
+ * context with capture on answers for its own frame; alone and batched give the same bits), imls_solve
+ * and imls_solve_correspondences — and the report (~1 KB) comes down with the result, into pinned
+ * memory.  imls_register_batch's own contexts never capture. */
+int imls_capture_pose_info(imls_ctx* ctx, int on);
+/* The report of the last solve sequence.  Never launches, never waits.  IMLS_ERR_STATE when capture
+ * was off for that sequence, or its result has not been collected yet. */
+int imls_pose_info(imls_ctx* ctx, struct imls_pose_info* out);
+
 /* Map FIFO kept in HBM: replaces accumulateTargetCloud(newCloud, max_queue_size, ...)
  * (laser_odometry.cpp:116-136, called at 663-664) followed by the next frame's
  * setTargetPointCloud(accumulatedTargetCloud) (509-510; imls_icp.cpp:80-103).  The new filtered
@@ -773,8 +847,9 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * candidate compaction), 11 = the sampler, compaction and cloud-assembly kernels of imls_sweep_process /
  * imls_sample_point_cloud_device (which record 5, 6, 7, 9 and 10 for the kernels they share with
  * the calls above), 12 = the deskew kernel (imls_deskew, imls_deskew_device, and the sweep's after
- * imls_sweep_set_motion).  enable: 0 off, 1 every kind above (the members of
- * an imls_register_frames batch then build their indices one by one, each inside its events),
+ * imls_sweep_set_motion), 13 = the pose-info kernels (imls_capture_pose_info; recorded with enable 1
+ * only).  enable: 0 off, 1 every kind above (the members of an imls_register_frames batch then build
+ * their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */
 int imls_enable_timing(imls_ctx* ctx, int enable);

@@ -200,6 +200,17 @@ public:
     // registerFrame starts at rPose = pose (the scan's predicted pose in the map frame); nullptr = I
     void setInitialPose(const double* pose) { detail::check(imls_set_initial_pose(ctx_, pose), ctx_); }
 
+    // The covariance slot IMLSICPMatcher::Match declares and only sets to identity (imls_icp.cpp:797-811):
+    // with capture on, poseInfo() after registerFrame returns the report of the frame's final solve
+    // (imls_gpu.h: a 6×6 covariance in (ωx, ωy, ωz, tx, ty, tz) order, the information matrix, its
+    // eigen-decomposition and rank, DRPM's probabilities).  Throws when capture was off for that frame.
+    void capturePoseInfo(bool on) { detail::check(imls_capture_pose_info(ctx_, on ? 1 : 0), ctx_); }
+    struct imls_pose_info poseInfo() const {
+        struct imls_pose_info info;
+        detail::check(imls_pose_info(ctx_, &info), ctx_);
+        return info;
+    }
+
     const uint64_t* rejectCounters() const { return reject_; }
     const imls_params& params() const { return params_; }
 

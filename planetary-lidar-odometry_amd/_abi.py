@@ -71,6 +71,38 @@ class ImlsIterTrace(C.Structure):
                 ("n_valid", C.c_uint64), ("n_kept", C.c_uint64)]
 
 
+IMLS_INFO_VALID, IMLS_INFO_RANK_DEFICIENT, IMLS_INFO_NO_DOF, IMLS_INFO_DRPM_RAN, IMLS_INFO_DRPM_DEGENERATE = 1, 2, 4, 8, 16
+IMLS_INFO_RANK_RELTOL = 1e-12
+
+
+class ImlsPoseInfo(C.Structure):
+    """Field-for-field mirror of `struct imls_pose_info` (include/imls_gpu.h)."""
+    _fields_ = [
+        ("hessian", _f64 * 36), ("gradient", _f64 * 6), ("x", _f64 * 6),
+        ("btb", _f64), ("rss", _f64), ("weight_sum", _f64), ("n_rows", C.c_uint64),
+        ("eigenvalues", _f64 * 6), ("eigenvectors", _f64 * 36),
+        ("sigma2", _f64), ("covariance", _f64 * 36), ("drpm_probability", _f64 * 6),
+        ("rank", _i32), ("iteration", _i32), ("status", _i32), ("solve_method", _i32), ("final_method", _i32),
+        ("flags", _u32), ("_reserved", _i32 * 2),
+    ]
+
+    def as_dict(self) -> dict:
+        """numpy arrays for the vectors and matrices (6×6 row-major; eigenvectors[k] = vector k), Python
+        scalars for the rest."""
+        import numpy as np
+        out = {}
+        for k, t in self._fields_:
+            if k.startswith("_"):
+                continue
+            v = getattr(self, k)
+            if hasattr(v, "_length_"):
+                a = np.array(v[:], dtype=np.float64)
+                out[k] = a.reshape(6, 6) if a.size == 36 else a
+            else:
+                out[k] = v
+        return out
+
+
 def default_params() -> ImlsParams:
     """The reference's shipped config.json values (laser_odometry section), matching
     imls_default_params() in the library; computed here too so CPU-only code needs no GPU."""
@@ -310,6 +342,8 @@ def _bind(lib: C.CDLL, strict: bool = True) -> C.CDLL:
         "imls_deskew": (C.c_int, [VP, VP, C.c_int32, C.c_float, VP, SZ, SZ, VP, SZ]),
         "imls_deskew_device": (C.c_int, [VP, VP, C.c_int32, C.c_float, VP, SZ, VP]),
         "imls_sweep_set_motion": (C.c_int, [VP, VP, C.c_int32]),
+        "imls_capture_pose_info": (C.c_int, [VP, C.c_int]),
+        "imls_pose_info": (C.c_int, [VP, P(ImlsPoseInfo)]),
     }
     for name, (res, args) in sig.items():
         if not strict and not hasattr(lib, name):
@@ -339,7 +373,7 @@ ABI_SYMBOLS = (
     "imls_default_curvature_params", "imls_presample_curvature", "imls_sample_three_axis", "imls_sample_random",
     "imls_default_sweep_params", "imls_sweep_process", "imls_sweep_process_device", "imls_sweep_reset",
     "imls_sweep_clouds_device", "imls_sweep_download", "imls_sample_point_cloud_device", "imls_shuffle_positions",
-    "imls_deskew", "imls_deskew_device", "imls_sweep_set_motion",
+    "imls_deskew", "imls_deskew_device", "imls_sweep_set_motion", "imls_capture_pose_info", "imls_pose_info",
 )
 
 _LIB = None

@@ -269,6 +269,76 @@ SolveLaunch solve_launch(imls_ctx* c, imls_iter_trace* tr, int update_pose) {
     return L;
 }
 
+// Pose-info capture (imls_capture_pose_info).  info_begin, ahead of a solve sequence of up to `rows`
+// rows: with capture off it clears SolveState::info (no solve exports, nothing else runs); with it on
+// it sizes the buffers, points the solves at the export block and clears that block on stream s.
+// Call it before the SolveState is copied into a launch (solve_launch, pair_dev).
+constexpr size_t kInfoOutOff = 256, kInfoSlabOff = 256 + (sizeof(struct imls_pose_info) + 255) / 256 * 256;
+static_assert(sizeof(InfoExport) <= kInfoOutOff, "export block");
+int info_begin(imls_ctx* c, int rows, hipStream_t s) {
+    c->info_state = 0;
+    c->st.info = nullptr;
+    if (!c->info_capture) return IMLS_OK;
+    if (!grow(c->info_mem, kInfoSlabOff + (size_t)info_blocks(rows) * kInfoTerms * 8))
+        return fail(c, IMLS_ERR_DEVICE, "hipMalloc (pose info)");
+    if (!c->h_info && hipHostMalloc((void**)&c->h_info, sizeof(struct imls_pose_info)) != hipSuccess)
+        return fail(c, IMLS_ERR_DEVICE, "hipHostMalloc (pose info)");
+    c->st.info = (InfoExport*)c->info_mem.p;
+    if (hipMemsetAsync(c->info_mem.p, 0, kInfoOutOff, s) != hipSuccess) return fail(c, IMLS_ERR_DEVICE, "hipMemset (pose info)");
+    return IMLS_OK;
+}
+
+// The pass itself, behind the solve sequence on stream s (timed as kind 13 on `timer`, the context
+// whose stream s is), and the report's copy into pinned memory.  method: the solve method of the
+// sequence; rows_d / weights: the fp64 rows of a host-API solve (null: the projection's float rows);
+// N: their count.  RANSAC reads its inlier rows where launch_solve left them.
+int info_enqueue(imls_ctx* c, imls_ctx* timer, hipStream_t s, int method, const double* rows_d, const double* weights, int N,
+                 int in_loop) {
+    if (!c->st.info) return IMLS_OK;
+    char* base = (char*)c->info_mem.p;
+    InfoLaunch L{};
+    L.N = N;
+    L.ex = c->st.info;
+    L.status = c->st.status;
+    L.iters = c->st.iters;
+    L.in_loop = in_loop;
+    L.solve_method = method;
+    L.slabs = (double*)(base + kInfoSlabOff);
+    L.out = (struct imls_pose_info*)(base + kInfoOutOff);
+    if (method == IMLS_SOLVE_RANSAC) {
+        const int cap = std::max(N, 1);
+        const RansacFrame F = ransac_frame(c->ransac_mem.p, cap, (int*)c->rng.p);
+        const bool unit = c->P.ransac_final_method == IMLS_FINAL_LS;
+        L.final_method = c->P.ransac_final_method;
+        L.N = cap;
+        L.rows_d = F.inl;
+        L.count = F.cnt_in;
+        L.weights = unit ? nullptr : F.inl + 9 * (size_t)cap;
+        L.wsum = unit ? nullptr : F.wsum;
+    } else if (rows_d) {
+        L.rows_d = rows_d;
+        L.weights = weights;
+    } else {
+        L.cs = (const float4*)c->cs.p;
+        L.cd = (const float4*)c->cd.p;
+        L.cn = (const float4*)c->cn.p;
+    }
+    int slot = -1;
+    if (timer->timing == 1) {             // (the light mode 2 keeps to the projection and solve events)
+        slot = ev_pair(timer);
+        if (slot >= 0) hipEventRecord(timer->ev[slot], s);
+    }
+    launch_pose_info(s, L);
+    if (slot >= 0) {
+        hipEventRecord(timer->ev[slot + 1], s);
+        timer->ev_pairs[kTimePoseInfo].push_back({slot, slot + 1});
+    }
+    if (hipMemcpyAsync(c->h_info, L.out, sizeof(struct imls_pose_info), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return fail(c, IMLS_ERR_DEVICE, "pose info download");
+    c->info_state = 1;
+    return IMLS_OK;
+}
+
 int ensure_trace(imls_ctx* c, int iters) {
     if (c->trace_cap >= iters && c->h_trace) return IMLS_OK;
     if (!grow(c->trace_mem, (size_t)std::max(iters, 1) * sizeof(imls_iter_trace))) return fail(c, IMLS_ERR_DEVICE, "hipMalloc (trace)");
@@ -606,6 +676,8 @@ void imls_destroy(imls_ctx* c) {
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     if (c->h_trace) (void)hipHostFree(c->h_trace);
     if (c->h_misc) (void)hipHostFree(c->h_misc);
+    if (c->h_info) (void)hipHostFree(c->h_info);
+    if (c->info_mem.p) (void)hipFree(c->info_mem.p);
     if (c->h_rng) (void)hipHostFree(c->h_rng);
     if (c->ev_rng) (void)hipEventDestroy(c->ev_rng);
     if (c->tab_h) (void)hipHostFree(c->tab_h);
@@ -906,20 +978,24 @@ int imls_project(imls_ctx* c, const double pose[16], float* x_out, float* y_out,
 
 int imls_solve(imls_ctx* c, double delta_out[16], int* ok) {
     if (!c || !delta_out) return IMLS_ERR_ARG;
+    c->info_state = 0;
     if (!c->has_corr) return fail(c, IMLS_ERR_STATE, "imls_project first");
     if (int rc = check_device(c)) return rc;
     hipMemsetAsync(c->st.done, 0, 16, c->stream);
     hipMemsetAsync(c->st.status, 0, 16, c->stream);
     if (int rc = prepare_ransac(c, c->N)) return rc;
+    if (int rc = info_begin(c, c->N, c->stream)) return rc;
     int slot;
     timed_begin(c, kTimeSolve, slot);
     launch_solve(c->stream, solve_launch(c, nullptr, 0));
     timed_end(c, kTimeSolve, slot);
+    if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 0)) return rc;
     int status = 0;
     hipMemcpyAsync(delta_out, c->st.delta, 16 * 8, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(&status, c->st.status, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, IMLS_ERR_DEVICE, "solve failed");
     harvest_timing(c);
+    if (c->info_state == 1) c->info_state = 2;
     if (ok) *ok = status == IMLS_FRAME_SOLVE_FAILED ? 0 : 1;
     return IMLS_OK;
 }
@@ -927,6 +1003,7 @@ int imls_solve(imls_ctx* c, double delta_out[16], int* ok) {
 int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, const double* d, const double* n,
                                const double* w, size_t N, double delta_out[16], int* ok) {
     if (!c || !s || !d || !n || !delta_out) return IMLS_ERR_ARG;
+    c->info_state = 0;
     if (method != IMLS_SOLVE_LS && method != IMLS_SOLVE_WEIGHTED_LS && method != IMLS_SOLVE_RANSAC &&
         method != IMLS_SOLVE_DRPM)
         return fail(c, IMLS_ERR_UNSUPPORTED, "method");
@@ -953,6 +1030,7 @@ int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, con
     if (rc0) return rc0;
     if (method == IMLS_SOLVE_DRPM && !grow(c->ransac_mem, ransac_bytes((int)std::max<size_t>(N, 1))))
         return fail(c, IMLS_ERR_DEVICE, "hipMalloc (DRPM)");
+    if (int rc = info_begin(c, (int)std::max<size_t>(N, 1), c->stream)) return rc;
     SolveLaunch L = solve_launch(c, nullptr, 0);
     L.N = (int)N;
     L.blocks1 = 0;
@@ -962,16 +1040,22 @@ int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, con
     L.weights = dw;
     L.rows_are_double = 1;
     launch_solve(c->stream, L);
+    if (int rc = info_enqueue(c, c, c->stream, method, r, dw, (int)N, 0)) return rc;
     int status = 0;
     hipMemcpyAsync(delta_out, c->st.delta, 16 * 8, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(&status, c->st.status, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, IMLS_ERR_DEVICE, "solve failed");
+    if (c->info_state == 1) {
+        harvest_timing(c);
+        c->info_state = 2;
+    }
     if (ok) *ok = status == IMLS_FRAME_SOLVE_FAILED ? 0 : 1;
     return IMLS_OK;
 }
 
 int imls_register_frame_async(imls_ctx* c) {
     if (!c) return IMLS_ERR_ARG;
+    c->info_state = 0;                    // whatever happens below, the previous frame's report is gone
     if (c->batch_member) return fail(c, IMLS_ERR_STATE, "the context is part of a pending batch");
     if (int rc = check_device(c)) return rc;
     if (int rc = ensure_built(c)) return rc;
@@ -989,6 +1073,7 @@ int imls_register_frame_async(imls_ctx* c) {
     if (int rc = ensure_map_normals(c)) return rc;
     const TreeView tv = tree_view(c);
     if (int rc = prepare_ransac(c, c->N)) return rc;
+    if (int rc = info_begin(c, c->N, c->stream)) return rc;
     c->cap_iters = 0;
     c->cap_run = -1;
     if (c->capture && iters > 0) {
@@ -1019,6 +1104,7 @@ int imls_register_frame_async(imls_ctx* c) {
         launch_solve(c->stream, solve_launch(c, tr + it, 1));
         timed_end(c, kTimeSolve, slot);
     }
+    if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 1)) return rc;
     k_frame_results<<<1, 256, 0, c->stream>>>(c->st.pose, c->st.iters, c->st.status, (const unsigned long long*)tr,
                                               iters * (int)(sizeof(imls_iter_trace) / 8), c->h_misc,
                                               (unsigned long long*)c->h_trace);
@@ -1036,6 +1122,7 @@ int imls_register_frame_result(imls_ctx* c, double pose_out[16], int* iters_run,
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, IMLS_ERR_DEVICE, std::string("frame failed: ") + hipGetErrorString(e));
     harvest_timing(c);
+    if (c->info_state == 1) c->info_state = 2;
     const int* misc = (const int*)(c->h_misc + 16);     // iters (pinned, copied by register_frame_async)
     const int st = *(const int*)(c->h_misc + 18);       // status
     if (pose_out) std::memcpy(pose_out, c->h_misc, 16 * 8);
@@ -1090,6 +1177,20 @@ int imls_captured_correspondences(imls_ctx* c, int iter, size_t cap, float* x_ou
         if (src_index_out) src_index_out[k] = (uint32_t)i;
         ++k;
     }
+    return IMLS_OK;
+}
+
+int imls_capture_pose_info(imls_ctx* c, int on) {
+    if (!c) return IMLS_ERR_ARG;
+    c->info_capture = on != 0;
+    return IMLS_OK;
+}
+
+int imls_pose_info(imls_ctx* c, struct imls_pose_info* out) {
+    if (!c || !out) return IMLS_ERR_ARG;
+    if (c->info_state == 1) return fail(c, IMLS_ERR_STATE, "collect the result first");
+    if (c->info_state != 2) return fail(c, IMLS_ERR_STATE, "pose-info capture was off for the last solve (imls_capture_pose_info)");
+    std::memcpy(out, c->h_info, sizeof(*out));
     return IMLS_OK;
 }
 

@@ -259,6 +259,7 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
     for (size_t k = 0; k < n; ++k) {
         imls_ctx* c = ctxs[k];
         if (!c) return fail(L, IMLS_ERR_ARG, "null context in the batch");
+        c->info_state = 0;                // the previous frame's report is gone, whatever happens below
         c->cap_iters = 0;                 // batched frames capture nothing: drop an older capture
         if (c->device != L->device) return fail(L, IMLS_ERR_ARG, "batch contexts must share one device");
         imls_params pc = c->P, pl = L->P;
@@ -356,6 +357,7 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         }
         if (int rc = check_tv_ready(c)) return fail(L, rc, "context " + std::to_string(k) + ": " + c->err);
         if (int rc = prepare_ransac(c, c->N)) return fail(L, rc, c->err);
+        if (int rc = info_begin(c, c->N, s)) return fail(L, rc, c->err);   // (its memset: ordered after the join below by the table's copy)
         L->tab_h[k] = pair_dev(c);
         std::memcpy(reinterpret_cast<double*>(L->tab_h + n) + 16 * k, c->init_pose, 16 * sizeof(double));
         L->tab_h[k].recompute_normals = need_nrm ? 1 : 0;
@@ -392,6 +394,10 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
             launch_solve_batch(s, tab, nh, (int)n, kp, it);
         timed_end(L, kTimeSolve, slot);
     }
+    // every capturing member's pose-info pass, the lone frame's two launches on the same rows: the
+    // same bits alone and batched
+    for (size_t k = 0; k < n; ++k)
+        if (int rc = info_enqueue(ctxs[k], L, s, kp.solve_method, nullptr, nullptr, ctxs[k]->N, 1)) return fail(L, rc, ctxs[k]->err);
     hs.mark("iterations");
     k_batch_results<<<(unsigned)std::min<size_t>(n, 1024), 64, 0, s>>>(tab, (int)n, (double*)L->res_d.p, std::max(iters, 0));
     hipMemcpyAsync(L->res_h, L->res_d.p, res_bytes, hipMemcpyDeviceToHost, s);
@@ -433,6 +439,8 @@ int frames_result(imls_ctx* L, double* poses_out, int32_t* iters_out, int32_t* s
     hipError_t e = hipStreamSynchronize(L->stream);
     if (e != hipSuccess) return fail(L, IMLS_ERR_DEVICE, std::string("batch failed: ") + hipGetErrorString(e));
     harvest_timing(L);
+    for (imls_ctx* m : L->members)
+        if (m->info_state == 1) m->info_state = 2;
     for (size_t k = 0; k < n; ++k) {
         const double* r = L->res_h + k * kResStride;
         if (poses_out) std::memcpy(poses_out + 16 * k, r, 16 * sizeof(double));

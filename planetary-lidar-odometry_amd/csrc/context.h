@@ -156,6 +156,12 @@ struct imls_ctx {
     DevBuf cap_mem;
     int cap_iters = 0, cap_N = 0;
     int cap_run = -1;                     // iterations the captured frame ran (-1: result not collected yet)
+    // pose covariance / degeneracy report (imls_capture_pose_info): info_mem = the solves' export block,
+    // the report and the row pass's slabs; h_info = the pinned copy the result call reads
+    bool info_capture = false;
+    DevBuf info_mem;
+    struct imls_pose_info* h_info = nullptr;
+    int info_state = 0;                   // 0: none (capture was off), 1: enqueued, result not collected, 2: ready
     // async frame results
     imls_iter_trace* h_trace = nullptr;   // pinned
     double* h_misc = nullptr;             // pinned: pose[16], iters, status
@@ -204,6 +210,9 @@ int fail(imls_ctx* c, int code, const std::string& m);
 bool grow(DevBuf& b, size_t bytes);
 bool grow_keep(DevBuf& b, size_t bytes, size_t keep, hipStream_t s);
 int check_device(imls_ctx* c);
+int info_begin(imls_ctx* c, int rows, hipStream_t s);
+int info_enqueue(imls_ctx* c, imls_ctx* timer, hipStream_t s, int method, const double* rows_d, const double* weights, int N,
+                 int in_loop);
 int check_tv_ready(imls_ctx* c);
 int ensure_solve(imls_ctx* c, int N);
 int ensure_trace(imls_ctx* c, int iters);

@@ -10,6 +10,7 @@
 //   correspondences, per source index (uncompacted): cs[N] = (x, valid), cd[N] = (y, ·),
 //                              cn[N] = (n, ·) float4 — source order is implicit in the index.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -175,6 +176,21 @@ __device__ __forceinline__ double wave_sum28(double (&a)[32]) {
     return a[0] + xor_f64(a[0], 1);
 }
 
+// What a solve leaves for the pose-info pass (pose_info.hip) — written ONLY through a non-null
+// SolveState::info (imls_capture_pose_info on), with ordinary vector stores: the two ends of a trimmed
+// solve's kept interval in the total order (|r₁| bits, row), the first solution the keys were taken
+// under, the vector the solve turned into Δ, DRPM's six probabilities.
+struct InfoExport {
+    unsigned long long key_lo, key_hi;
+    unsigned row_lo, row_hi;
+    double x0[6], x[6], prob[6];
+    int kind;                 // InfoKind of the last solve that succeeded (0: none since the reset)
+    int iteration;            // the trace index of that solve
+    int degenerate;           // DRPM took the SNR-weighted branch
+    int pad;
+};
+enum InfoKind { kInfoNone = 0, kInfoAll = 1, kInfoTrim = 2, kInfoDrpm = 3 };
+
 // Solver scratch living in device memory (one per context).
 struct SolveState {
     double* pose;             // [16] current rPose
@@ -196,6 +212,7 @@ struct SolveState {
     double* keys;             // [N] |r|
     imls_iter_trace* trace;   // [iterations]
     int partial_cap;
+    InfoExport* info;         // null unless pose-info capture is on (then every solve exports)
 };
 
 // RANSAC state of one context (ransac.hip), carved from its RANSAC scratch by ransac_frame().
@@ -282,6 +299,7 @@ __device__ __forceinline__ PairDev device_view(const PairDev* pa) {
     IMLS_GLOBAL_FIELD(A, pa, st.cand_lo); IMLS_GLOBAL_FIELD(A, pa, st.cand_lo_row); IMLS_GLOBAL_FIELD(A, pa, st.cand_hi);
     IMLS_GLOBAL_FIELD(A, pa, st.cand_hi_row); IMLS_GLOBAL_FIELD(A, pa, st.sel); IMLS_GLOBAL_FIELD(A, pa, st.partial1);
     IMLS_GLOBAL_FIELD(A, pa, st.partial2); IMLS_GLOBAL_FIELD(A, pa, st.keys); IMLS_GLOBAL_FIELD(A, pa, st.trace);
+    IMLS_GLOBAL_FIELD(A, pa, st.info);
     return A;
 }
 
@@ -447,6 +465,25 @@ void launch_solve_batch(hipStream_t s, const PairDev* tab, const int* n_host, in
                         int src = 0);
 // pass 1 over every frame's RANSAC inlier rows (weighted: w / Σw)
 void launch_rows_pass1_batch(hipStream_t s, const PairDev* tab, const int* cap_host, int npairs, int weighted);
+
+// pose_info.hip — the covariance / degeneracy report of the last solve (imls_capture_pose_info)
+struct InfoLaunch {
+    const float4 *cs, *cd, *cn;        // float rows of the projection, or
+    const double* rows_d;              // fp64 rows [s 3n | d 3n | n 3n] (weights, count, wsum as Rows takes them)
+    const double* weights;
+    const int* count;
+    const double* wsum;
+    int N;                             // rows to visit
+    const InfoExport* ex;
+    const int *status, *iters;         // the frame's (SolveState)
+    int in_loop;                       // a registration (its iteration must be the frame's last)
+    int solve_method, final_method;
+    double* slabs;                     // [info_blocks(N) × kInfoTerms]
+    struct imls_pose_info* out;               // device
+};
+constexpr int kInfoTerms = 32;         // 21 H + 6 g + btb + Σw + rows + rss (+ 1 unused)
+inline int info_blocks(int N) { return (std::max(N, 1) + kBlock - 1) / kBlock; }
+void launch_pose_info(hipStream_t s, const InfoLaunch& L);
 
 // normals.hip — map normals recomputed from the map (get_normals=false, count mode), Morton order
 int launch_map_normals(hipStream_t s, const TreeView& t, int K, double r_normal, float4* out);
@@ -619,7 +656,8 @@ enum TimingKind {
     kTimeCurvature = 10,  // imls_presample_curvature
     kTimeSweep = 11,      // sweep sampler / compaction / cloud assembly (recorded by sweep.hip)
     kTimeDeskew = 12,     // deskew kernel
-    kTimingKinds = 13
+    kTimePoseInfo = 13,   // pose-info kernels (k_info_rows, k_info_final)
+    kTimingKinds = 14
 };
 // timing hook of the caller: a pair of events that will be harvested as `kind`, or false (timing off)
 typedef bool (*SweepMark)(void* owner, int kind, hipEvent_t ev[2]);

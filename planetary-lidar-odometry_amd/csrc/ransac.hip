@@ -1019,6 +1019,11 @@ __device__ __forceinline__ void drpm_solve_wave0(const SolveState& st, const Drp
     double D[16];
     delta_from_x(x, D);
     finish_iteration(st, tr, D, (double)*count_all, (double)*count_in, update_pose, kp);
+    if (st.info) {
+        for (int k = 0; k < 6; ++k) st.info->prob[k] = prob[k];
+        st.info->degenerate = pmin < threshold ? 1 : 0;
+        info_export(st.info, kInfoDrpm, x, st, update_pose);
+    }
 }
 
 __device__ __forceinline__ void drpm_final_body(int blocks, const SolveState& st, const DrpmDev& Dv, imls_iter_trace* tr,

@@ -351,6 +351,10 @@ __device__ void final_block(const Rows& rows, int N, SolveState st, imls_iter_tr
             for (int i = threadIdx.x; i < (int)n; i += NT) {
                 const long long rank = base + i;
                 if (rank >= lo && rank <= hi) add_row(cr[i]);
+                if (st.info) {            // the kept interval's two ends, for the pose-info pass
+                    if (rank == lo) { st.info->key_lo = ck[i]; st.info->row_lo = cr[i]; }
+                    if (rank == hi) { st.info->key_hi = ck[i]; st.info->row_hi = cr[i]; }
+                }
             }
             __syncthreads();
             FSTAMP(2);
@@ -360,6 +364,10 @@ __device__ void final_block(const Rows& rows, int N, SolveState st, imls_iter_tr
         rank_select(st.keys, N, lo, &selk[0], &selr[0], &shc);
         rank_select(st.keys, N, hi, &selk[1], &selr[1], &shc);
         __syncthreads();
+        if (st.info && threadIdx.x == 0) {
+            st.info->key_lo = selk[0]; st.info->row_lo = selr[0];
+            st.info->key_hi = selk[1]; st.info->row_hi = selr[1];
+        }
         for (int i = threadIdx.x; i < N; i += NT) {
             const double key = st.keys[i];
             if (key < 0) continue;
@@ -383,6 +391,10 @@ __device__ void final_block(const Rows& rows, int N, SolveState st, imls_iter_tr
     delta_from_x(x, D);
     FSTAMP(5);
     finish_iteration(st, tr, D, (double)st.sel[6], out[27], update_pose, kp);
+    if (st.info) {
+        for (int k = 0; k < 6; ++k) st.info->x0[k] = st.x0[k];
+        info_export(st.info, kInfoTrim, x, st, update_pose);
+    }
     FSTAMP(6);
 }
 
@@ -613,6 +625,7 @@ __device__ __forceinline__ void solve_small_body(const Rows& rows, int N, const 
                     double D[16];
                     delta_from_x(x, D);
                     finish_iteration(st, tr, D, nvalid, nvalid, update_pose, kp);
+                    if (st.info) info_export(st.info, kInfoAll, x, st, update_pose);
                     stop = 1;
                 }
                 for (int k = 0; k < 6; ++k) xs[k] = x[k];
@@ -725,6 +738,10 @@ __device__ __forceinline__ void solve_small_body(const Rows& rows, int N, const 
             rows.get((int)qr[q], a, bb, wt);
             add_row(a, bb);
         }
+        if (st.info) {                // the kept interval's two ends (the keys live in LDS only)
+            if (rank == lo) { st.info->key_lo = qk[q]; st.info->row_lo = qr[q]; }
+            if (rank == hi) { st.info->key_hi = qk[q]; st.info->row_hi = qr[q]; }
+        }
     }
     block_sum28<kSmallBlock>(loc, red, acc);
     DBG_STAMP(4);
@@ -736,6 +753,10 @@ __device__ __forceinline__ void solve_small_body(const Rows& rows, int N, const 
     delta_from_x(x, D);
     DBG_STAMP(6);
     finish_iteration(st, tr, D, (double)n, acc[27], update_pose, kp);
+    if (st.info) {
+        for (int k = 0; k < 6; ++k) st.info->x0[k] = xs[k];
+        info_export(st.info, kInfoTrim, x, st, update_pose);
+    }
     DBG_STAMP(7);
 }
 

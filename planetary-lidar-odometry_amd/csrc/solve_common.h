@@ -385,6 +385,16 @@ __device__ inline void finish_iteration(SolveState st, imls_iter_trace* tr, cons
 }
 
 
+// What a successful solve leaves for the pose-info pass (thread 0, after finish_iteration; `ex` is
+// SolveState::info, non-null only while imls_capture_pose_info is on): the vector that became Δ, the
+// membership rule of its rows and the trace index of the iteration.
+__device__ __forceinline__ void info_export(InfoExport* ex, int kind, const double x[6], const SolveState& st,
+                                            int update_pose) {
+    for (int k = 0; k < 6; ++k) ex->x[k] = x[k];
+    ex->kind = kind;
+    ex->iteration = update_pose ? *st.iters - 1 : 0;
+}
+
 // The first LS solve (or the only one, weighted LS) over `blocks` pass-1 slabs, by one block of
 // NT threads: reduce, too-few gate (laser_odometry.cpp:570-576), solve6, and for LS the trim
 // ranks (solver.cpp:118-134, Q11) for the selection that follows.  red: LDS [(NT/64)·28],
@@ -418,6 +428,7 @@ __device__ void solve_first_block(const double* __restrict__ partial, int blocks
         double D[16];
         delta_from_x(x, D);
         finish_iteration(st, tr, D, nvalid, nvalid, update_pose, kp);
+        if (st.info) info_export(st.info, kInfoAll, x, st, update_pose);
         return;
     }
     for (int k = 0; k < 6; ++k) st.x0[k] = x[k];

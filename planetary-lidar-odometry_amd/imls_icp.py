@@ -90,6 +90,8 @@ class ImlsContext:
                                                        "(the GPU path has no CPU fallback)")
         self.n_target = 0
         self.n_source = 0
+        self._pose_info_on = False
+        self.last_info = None           # register_frames_result: this context's frame's pose-info report
 
     # -- plumbing -------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -286,8 +288,11 @@ class ImlsContext:
         trace = (_abi.ImlsIterTrace * it)()
         pose = np.zeros(16); iters = C.c_int(); status = C.c_int()
         self._check(self.lib.imls_register_frame(self.ctx, _ptr(pose), C.byref(iters), C.byref(status), trace))
-        return dict(pose=pose.reshape(4, 4), iters=iters.value, status=status.value,
-                    trace=[trace[k] for k in range(iters.value)])
+        out = dict(pose=pose.reshape(4, 4), iters=iters.value, status=status.value,
+                   trace=[trace[k] for k in range(iters.value)])
+        if self._pose_info_on:
+            out["info"] = self.pose_info()
+        return out
 
     def register_frame_async(self):
         self._check(self.lib.imls_register_frame_async(self.ctx))
@@ -532,6 +537,22 @@ class ImlsContext:
         for k, v in opts.items():
             self.set_option(k, v)
 
+    def capture_pose_info(self, on=True):
+        """Covariance / degeneracy report of every later solve sequence (imls_capture_pose_info);
+        register_frame()'s dict then carries it as `info`."""
+        self._check(self.lib.imls_capture_pose_info(self.ctx, int(bool(on))))
+        self._pose_info_on = bool(on)
+
+    def pose_info(self) -> dict:
+        """The report of the last solve sequence (imls_pose_info; include/imls_gpu.h defines the
+        fields): 6×6 arrays `hessian`, `covariance`, `eigenvectors` (row k = vector k), 6-vectors
+        `gradient`, `x`, `eigenvalues`, `drpm_probability`, scalars for the rest.  Parameter order
+        (ωx, ωy, ωz, tx, ty, tz).  ImlsError(IMLS_ERR_STATE) when capture was off for that sequence or
+        its result has not been collected."""
+        rec = _abi.ImlsPoseInfo()
+        self._check(self.lib.imls_pose_info(self.ctx, C.byref(rec)))
+        return rec.as_dict()
+
     def capture_correspondences(self, on=True):
         """Keep every iteration's correspondences of register_frame (imls_capture_correspondences)."""
         self._check(self.lib.imls_capture_correspondences(self.ctx, int(bool(on))))
@@ -626,7 +647,8 @@ class TraceView:
 
 def register_frames_result(contexts):
     """(poses (n,4,4), iterations (n,), statuses (n,), traces [n sequences of ImlsIterTrace]).  The
-    per-frame trace sequences are views into the batch's result array (records built on access)."""
+    per-frame trace sequences are views into the batch's result array (records built on access).
+    Each context's `last_info` is its frame's pose-info report (None with capture off)."""
     lead, n = contexts[0], len(contexts)
     it = max(lead.params.iterations, 1)
     poses = np.zeros((n, 16)); iters = np.zeros(n, np.int32); st = np.zeros(n, np.int32)
@@ -635,6 +657,8 @@ def register_frames_result(contexts):
     traces = [TraceView(tr, k * it, int(iters[k])) for k in range(n)]
     for c, t in zip(contexts, traces):
         c.last_trace = t
+        # each capturing member answers for its own frame (ImlsContext.capture_pose_info)
+        c.last_info = c.pose_info() if c._pose_info_on else None
     return poses.reshape(n, 4, 4), iters, st, traces
 
 
@@ -878,6 +902,33 @@ def inv_pose(T) -> np.ndarray:
     return out
 
 
+def adjoint(T) -> np.ndarray:
+    """The 6×6 adjoint of a rigid pose in (ω, t) order, [[R, 0], [t^·R, R]]: Exp(ξ)·T = T·Exp(Ad(T⁻¹)·ξ),
+    i.e. a left perturbation ξ seen through T on its right becomes Ad(T)·ξ on its left."""
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    R, t = T[:3, :3], T[:3, 3]
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    A = np.zeros((6, 6))
+    A[:3, :3] = R
+    A[3:, :3] = tx @ R
+    A[3:, 3:] = R
+    return A
+
+
+def propagate_covariance(Sigma_prev, T_prev, Sigma_rel) -> np.ndarray:
+    """Covariance of nowPose = prevPose·rPose under left perturbations, the two taken as independent:
+    Σ_prev + Ad(T_prev)·Σ_rel·Ad(T_prev)ᵀ (first order), all in (ω, t) order."""
+    A = adjoint(T_prev)
+    return np.asarray(Sigma_prev, dtype=np.float64).reshape(6, 6) + A @ np.asarray(Sigma_rel, dtype=np.float64).reshape(6, 6) @ A.T
+
+
+def covariance_to_ros(Sigma) -> np.ndarray:
+    """The 6×6 (ω, t) covariance as the row-major 36-vector of a geometry_msgs/PoseWithCovariance:
+    (x, y, z, rotation about x, y, z)."""
+    order = [3, 4, 5, 0, 1, 2]
+    return np.asarray(Sigma, dtype=np.float64).reshape(6, 6)[np.ix_(order, order)].reshape(36).copy()
+
+
 class LaserOdometry:
     """processData (laser_odometry.cpp:416-683) minus ROS: per (filteredLaserCloud, flatCloud)
     frame, the first frame only seeds the map (Q13); every later frame registers its flat cloud
@@ -911,12 +962,24 @@ class LaserOdometry:
     (measured 2.26°, 1.21°, 0.61° at 3° per sweep), because a deskew with a motion error δ leaves a
     shear the next registration absorbs half of.  When the platform is already moving at the first
     sweeps, give `initial_motion`, or an explicit `motion` for them.  Deskewing makes the clouds and
-    the map geometrically correct; it is not a claim about trajectory accuracy."""
+    the map geometrically correct; it is not a claim about trajectory accuracy.
+
+    pose_info=True turns the covariance / degeneracy report on in every context (both, when
+    pipelined).  `.infos` then holds one entry per registered frame — the report of that frame's final
+    solve (ImlsContext.pose_info), or None for a frame that did not register or whose report is not
+    valid — and `.pose_covariances` the covariance of each nowPose, chained by propagate_covariance
+    from a zero covariance at the first pose.  A frame without a valid report adds nothing to the chain,
+    although its pose may have moved (a frame that ends TOO_FEW or SOLVE_FAILED after good iterations
+    returns their pose and no report): every such frame's index into `.infos` is appended to
+    `.covariance_gaps`, and from the first gap on `.pose_covariances` is a lower bound only.  In "compensated" mode the report is about the pose in the map frame; the
+    relative covariance is Ad(inv(T_A))·Σ·Ad(inv(T_A))ᵀ before chaining.  The report is the formal
+    covariance of one linear solve (include/imls_gpu.h says what that leaves out): frames are taken
+    as independent, and a rank-deficient frame contributes zero along its unobserved directions."""
 
     def __init__(self, params: Optional[_abi.ImlsParams] = None, device: int = 0, pose_file: Optional[str] = None,
                  output_dir: Optional[str] = None, pipelined: Optional[bool] = None, map_model: str = "raw",
                  motion_prior: str = "none", rebase_distance: float = 100.0, producer=None, deskew: str = "none",
-                 initial_motion=None):
+                 initial_motion=None, pose_info: bool = False):
         self.producer = producer        # a producer.ScanRegistration: process_sweep's raw sweep → device clouds
         self.last_sweep = None
         if deskew not in ("none", "constant_velocity"):
@@ -959,6 +1022,14 @@ class LaserOdometry:
             os.makedirs(os.path.join(output_dir, "matched_points"), exist_ok=True)
             for c in self._ctxs:
                 c.capture_correspondences(True)
+        self.pose_info = bool(pose_info)
+        if self.pose_info:
+            for c in self._ctxs:
+                c.capture_pose_info(True)
+        self.infos: list = []           # pose_info: the report of each registered frame (or None)
+        self.pose_covariances: list = []   # pose_info: the chained 6×6 covariance of each nowPose
+        self.covariance_gaps: list = []    # pose_info: indices into infos of the frames that added nothing
+        self._cov = np.zeros((6, 6))
         self.prev_pose = np.eye(4)
         self.frame_count = 0
         self.pose_file = pose_file
@@ -1052,10 +1123,26 @@ class LaserOdometry:
                 pushed = True
                 pose, iters, status = ctx.register_frame_result()
                 result = dict(pose=pose, iters=iters, status=status, trace=ctx.last_trace)
+                if self.pose_info:
+                    result["info"] = ctx.pose_info()
             else:
                 result = ctx.register_frame()
             if registers and self.output_dir:
                 self._save_iterations(result, timestamp)
+            if self.pose_info:
+                info = result.get("info")
+                if info is not None and not info["flags"] & _abi.IMLS_INFO_VALID:
+                    info = None
+                self.infos.append(info)
+                if info is None:
+                    self.covariance_gaps.append(len(self.infos) - 1)
+                else:
+                    rel = info["covariance"]
+                    if posed:                          # the report is about T_A' in the map frame
+                        A = adjoint(inv_pose(self.anchor_pose))
+                        rel = A @ rel @ A.T
+                    self._cov = propagate_covariance(self._cov, self.prev_pose, rel)
+                self.pose_covariances.append(self._cov.copy())
             if registers and posed:
                 # the registration gave this scan's pose in the map frame: rPose = inv(T_A)·T_A'
                 result["map_pose"] = result["pose"]

@@ -3,7 +3,7 @@
   (a) ScanRegistration.process_raw + LaserOdometry.process — every cloud through host memory;
   (b) LaserOdometry.process_sweep — the clouds stay in HBM (imls_sweep_process).
 
-    python tools/sweep_bench.py [--frames 12] [--warmup 2] [--rounds 3] [--paths ab] [--deskew] [--out FILE.json]
+    python tools/sweep_bench.py [--frames 12] [--warmup 2] [--rounds 3] [--paths ab] [--deskew] [--pose-info] [--out FILE.json]
 
 Both paths run in alternated rounds in one process on one GPU, for the LS solver and the shipped
 RANSAC→DRPM.  Per path and solver: the median over the rounds of each round's median ms per frame
@@ -18,6 +18,9 @@ this times the launch, it does not improve these clouds).  "geometry" (always): 
 sensor model, its filtered cloud (front end → [deskew with the true motion] → ring PCA rows) expressed
 in the sweep-end frame against the generator's world hits — max and median distance in metres, with
 and without the deskew.
+--pose-info runs the same passes with the covariance / degeneracy report captured for every frame
+(LaserOdometry(pose_info=True)); the timing pass then also gives kind 13 (the pose-info kernels) per frame,
+read from the driver's contexts.
 --paths a runs the comparator alone (e.g. against another build of the library through
 IMLS_LIB_PATH)."""
 import argparse
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--paths", default="ab", choices=["ab", "a", "b"])
     ap.add_argument("--model", default="hdl64", choices=["hdl64", "vlp16"])
     ap.add_argument("--deskew", action="store_true", help="a fixed motion set for every sweep (both paths)")
+    ap.add_argument("--pose-info", action="store_true", help="capture the pose-info report of every frame")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -91,10 +95,13 @@ def main():
         """One pass over the stream → per-frame ms (total, producer), sweep infos, kernel times, poses."""
         sr = producer.ScanRegistration(shuffle_seed=4, rand_seed=2)
         ms, prod, infos = [], [], []
-        with imls_icp.LaserOdometry(params(solver), device=0, producer=sr if path == "b" else None) as lo:
+        with imls_icp.LaserOdometry(params(solver), device=0, producer=sr if path == "b" else None,
+                                    pose_info=a.pose_info) as lo:
             if timing:
                 sr.ctx.enable_timing(1)
                 sr.ctx.reset_timing()
+                if a.pose_info:
+                    lo.apply(lambda c: c.enable_timing(1))
             if path == "b":
                 plain = sr.process_raw_device
 
@@ -124,6 +131,10 @@ def main():
                         kern[name] = "not measured"
                         continue
                     kern[name] = dict(ms_per_frame=round(t / total, 4), launches_per_frame=round(n / total, 2))
+                if a.pose_info:
+                    tn = [c.kernel_timing(13) for c in lo.contexts]
+                    kern["pose_info"] = dict(ms_per_frame=round(sum(t for t, _ in tn) / total, 4),
+                                             launches_per_frame=round(sum(n for _, n in tn) / total, 2))
             poses = [now.tobytes() for _, now in lo.poses]
             iters = [r[2] for r in lo.results]
         sr.close()
@@ -133,7 +144,8 @@ def main():
     paths = list(a.paths)
     solvers = ("ls", "ransac_drpm")
     res = dict(tool="sweep_bench", sensor=a.model, frames=a.frames, warmup=a.warmup, rounds=a.rounds,
-               raw_points=int(np.mean([len(r) for r in raws])), deskew=bool(a.deskew), solvers={})
+               raw_points=int(np.mean([len(r) for r in raws])), deskew=bool(a.deskew), pose_info=bool(a.pose_info),
+               solvers={})
     for solver in solvers:
         for pth in paths:              # warm-up: buffers grown, code objects loaded
             run(pth, solver, False)
