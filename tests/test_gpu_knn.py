@@ -15,7 +15,7 @@ import pathlib
 import numpy as np
 import pytest
 
-import imls_np
+import index_edge_cases
 import oracle_ctypes as oc
 from planetary_lidar_odometry_amd import _abi, config, imls_icp, synth
 
@@ -108,20 +108,8 @@ def lattice():
 
 
 def brute(tgt6, q, k, r, self_ok):
-    P = tgt6[:3].T
-    idx = np.full((len(q), k), -1, np.int32)
-    d2o = np.full((len(q), k), np.inf)
-    for i, x in enumerate(q):
-        d2 = imls_np.exact_d2(x, P)
-        ii = np.arange(len(P))
-        m = d2 <= r * r
-        if not self_ok:
-            m &= d2 > np.finfo(np.float64).eps
-        d2, ii = d2[m], ii[m]
-        o = np.lexsort((ii, d2))[:k]
-        idx[i, : len(o)] = ii[o]
-        d2o[i, : len(o)] = d2[o]
-    return idx, d2o
+    """The shared brute force (index_edge_cases.brute_knn) on an SoA target."""
+    return index_edge_cases.brute_knn(tgt6[:3].T, q, k, r, self_ok)
 
 
 @pytest.mark.parametrize("self_ok", [0, 1])
