@@ -149,7 +149,7 @@ int ensure_solve(imls_ctx* c, int N) {
     size_t n = (size_t)std::max(N, 1);
     n += n / 4 + 64;                      // headroom (see grow): the next frames' N differ a little
     // deferred (uncertified) queries: k_finish's wave w writes its count to word w and its queries,
-    // in slot order, to the region fb_off + w·64 (project.hip finish_body, k_project_lane)
+    // in slot order, to the region fb_off + w·64 (finish.hip finish_body, k_project_lane)
     const size_t nfb = (n + 63) / 64;
     c->fb_off = (nfb + 63) / 64 * 64;
     if (!grow(c->cs, n * 16) || !grow(c->cd, n * 16) || !grow(c->cn, n * 16) || !grow(c->fb, (c->fb_off + nfb * 64) * 4))
@@ -250,6 +250,35 @@ int ensure_map_normals(imls_ctx* c) {
     c->rnr_k = c->P.search_number_normal;
     c->rnr_r = c->P.r_normal;
     return IMLS_OK;
+}
+
+// the context's frame as a projection launch: at `pose` / `done`, trace slot tr, list reuse
+// (use_prev) against the last increment `delta`
+ProjectLaunch project_launch(imls_ctx* c, const TreeView& t, const KParams& kp, const double* pose, const int* done,
+                             imls_iter_trace* tr, const double* delta, int use_prev, hipEvent_t* marks) {
+    ProjectLaunch L{};
+    L.t = t;
+    L.spt = (const float4*)c->spt.p;
+    L.snr = (const float4*)c->snr.p;
+    L.qperm = (const unsigned*)c->qperm.p;
+    L.N = c->N;
+    L.pose = pose;
+    L.done = done;
+    L.delta = delta;
+    L.kp = kp;
+    L.cs = (float4*)c->cs.p;
+    L.cd = (float4*)c->cd.p;
+    L.cn = (float4*)c->cn.p;
+    L.partial1 = c->st.partial1;
+    L.tr = tr;
+    L.stats = stats_ptr(c);
+    L.fb_list = fb_list(c);
+    L.fb_count = fb_count(c);
+    L.lists = (int*)c->prevnn.p;
+    L.lane_mode = c->lane_mode;
+    L.use_prev = use_prev;
+    L.marks = marks;
+    return L;
 }
 
 SolveLaunch solve_launch(imls_ctx* c, imls_iter_trace* tr, int update_pose) {
@@ -946,10 +975,8 @@ int imls_project(imls_ctx* c, const double pose[16], float* x_out, float* y_out,
     int slot;
     hipEvent_t marks[3];
     timed_begin(c, kTimeProject, slot);
-    launch_project(c->stream, tree_view(c), (const float4*)c->spt.p, (const float4*)c->snr.p, (const unsigned*)c->qperm.p,
-                   c->N, dpose, dzero, c->kp, (float4*)c->cs.p, (float4*)c->cd.p, (float4*)c->cn.p, c->st.partial1,
-                   c->st.trace, stats_ptr(c), fb_list(c), fb_count(c), c->lane_mode,
-                   nullptr, (int*)c->prevnn.p, 0, project_marks(c, marks));
+    launch_project(c->stream,
+                   project_launch(c, tree_view(c), c->kp, dpose, dzero, c->st.trace, nullptr, 0, project_marks(c, marks)));
     timed_end(c, kTimeProject, slot);
     std::vector<float> hs((size_t)c->N * 4), hd((size_t)c->N * 4), hn((size_t)c->N * 4);
     imls_iter_trace tr;
@@ -1085,10 +1112,8 @@ int imls_register_frame_async(imls_ctx* c) {
         int slot;
         hipEvent_t marks[3];
         timed_begin(c, kTimeProject, slot);
-        launch_project(c->stream, tv, (const float4*)c->spt.p, (const float4*)c->snr.p, (const unsigned*)c->qperm.p, c->N,
-                       c->st.pose, c->st.done, kp_at(c->kp, it), (float4*)c->cs.p, (float4*)c->cd.p, (float4*)c->cn.p,
-                       c->st.partial1, tr + it, stats_ptr(c), fb_list(c), fb_count(c), c->lane_mode,
-                       c->st.delta, (int*)c->prevnn.p, it > 0 && c->temporal_seed, project_marks(c, marks));
+        launch_project(c->stream, project_launch(c, tv, kp_at(c->kp, it), c->st.pose, c->st.done, tr + it, c->st.delta,
+                                                 it > 0 && c->temporal_seed, project_marks(c, marks)));
         timed_end(c, kTimeProject, slot);
         if (c->cap_iters) {   // this iteration's correspondences (stale, and never read, once the frame stopped)
             char* dst = (char*)c->cap_mem.p + (size_t)it * c->N * 48;

@@ -1,4 +1,4 @@
-// geom.h — device geometry shared by the matching kernels (project.hip, tv.hip): the fp32 box
+// geom.h — device geometry shared by the matching kernels (project_common.h, tv.hip): the fp32 box
 // distance used for pruning, the exact libnabo metric and the per-iteration source transform.
 #pragma once
 #include "internal.h"

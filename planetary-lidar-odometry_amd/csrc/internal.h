@@ -67,7 +67,7 @@ struct KParams {
     int proj;                 // projected-distance candidate rule (brute force in the reference)
     double gate_dist, gate_proj;   // proj mode: ‖p−x‖ < gate_dist and ‖(p−x)×n_s‖ < gate_proj
     // traversal tuning: documented runtime options (imls_set_option, include/imls_gpu.h), fixed
-    // constants otherwise (project.hip: kSeedHalf, kReseed, kSparseLanes, kWide)
+    // constants otherwise (project_common.h: kSeedHalf, kReseed, kSparseLanes, kWide)
     int qwave;                // traversal: −1 auto (one wave per query up to kQwaveAutoN queries), 0 packets, 1 wave per query
     int packet;               // packet traversal: queries per wave in this launch (64, or 32 / 16: see pk_small)
     int pk_small, pk_iters;   // the first pk_iters ICP iterations (mostly seeding lanes) use pk_small-query packets
@@ -397,23 +397,53 @@ int fifo_index(hipStream_t s, const unsigned long long* mkey, const unsigned* mv
 // project.hip
 // k_knn_wave → k_finish (+ the exact k_project_lane fallback for uncertified queries); lane_mode
 // runs every query through k_project_lane.  partial1 receives project_blocks(N) slabs.
-void launch_project(hipStream_t s, const TreeView& t, const float4* spt, const float4* snr,
-                    const unsigned* qperm, int N, const double* pose, const int* done, const KParams& kp,
-                    float4* cs, float4* cd, float4* cn, double* partial1, imls_iter_trace* tr,
-                    unsigned long long* nbr_stats, unsigned* fb_list, unsigned* fb_count, int lane_mode,
-                    const double* delta, int* lists, int use_prev, hipEvent_t* marks = nullptr);
-// delta: last pose increment (read when use_prev); lists: [KL][N] positions + [N] worst keys,
-// kept across ICP iterations (temporal seed); marks: 3 events recorded before k_knn_wave, between
-// it and k_finish, and after k_finish (timing), or null
+struct ProjectLaunch {
+    TreeView t;
+    const float4 *spt, *snr;
+    const unsigned* qperm;
+    int N;
+    const double* pose;
+    const int* done;
+    const double* delta;               // last pose increment (read when use_prev)
+    KParams kp;
+    float4 *cs, *cd, *cn;
+    double* partial1;                  // project_blocks(N) slabs
+    imls_iter_trace* tr;               // the iteration's trace slot
+    unsigned long long* stats;
+    unsigned *fb_list, *fb_count;
+    int* lists;                        // the frame's list block (ListBlock), kept across ICP iterations (temporal seed)
+    int lane_mode, use_prev;
+    hipEvent_t* marks;                 // 3 events recorded before k_knn_wave, between it and k_finish, and
+                                       // after k_finish (timing), or null
+};
+#pragma GCC visibility push(hidden)
+void launch_project(hipStream_t s, const ProjectLaunch& L);
+#pragma GCC visibility pop
 constexpr int kMaxKL = 46;       // list entries per query at most (the lone-frame path: K + 12 for K ≤ 32, capped)
-// per-query reference position + list guarantee (float4 xref[N]) and the key the list's answer
-// relied on (float nref[N]), after the [kMaxKL+1][N] list block
-__host__ __device__ inline float4* xref_of(int* lists, int N) {
-    return reinterpret_cast<float4*>(reinterpret_cast<char*>(lists) + ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256);
+// The list block of a frame of N queries whose lists hold KL entries: the positions pos[KL][N] (row
+// pitch N) with the worst keys wlist[N] as row KL, then — after kMaxKL + 1 rows, whatever KL is — the
+// per-query reference position + list guarantee xref[N] and the key the list's answer relied on
+// nref[N]; a kNN query set's block ends with the deferred queries' search caps[N].  256-B aligned parts.
+struct ListBlock {
+    int* pos;
+    float* wlist;
+    float4* xref;
+    float* nref;
+    float* caps;                       // kNN blocks only (knn_list_bytes)
+    static __host__ __device__ size_t part(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    static __host__ __device__ size_t pos_bytes(int N) { return part((size_t)(kMaxKL + 1) * N * 4); }
+    static __host__ __device__ size_t bytes(int N) { return pos_bytes(N) + part((size_t)N * 20) + 512; }
+};
+__host__ __device__ inline ListBlock list_block(int* lists, int N, int KL) {
+    ListBlock b;
+    b.pos = lists;
+    b.xref = reinterpret_cast<float4*>(reinterpret_cast<char*>(lists) + ListBlock::pos_bytes(N));
+    b.wlist = reinterpret_cast<float*>(lists + (size_t)KL * N);
+    b.nref = reinterpret_cast<float*>(b.xref + N);
+    b.caps = reinterpret_cast<float*>(reinterpret_cast<char*>(lists) + ListBlock::bytes(N));
+    return b;
 }
-inline size_t prevnn_bytes(int N) {
-    return ((size_t)(kMaxKL + 1) * N * 4 + 255) / 256 * 256 + ((size_t)N * 20 + 255) / 256 * 256 + 512;
-}
+inline size_t prevnn_bytes(int N) { return ListBlock::bytes(N); }
 // Public kNN query (imls_knn / imls_knn_device): the same two stages over a query set of its own.
 // knn_prepare: queries (component c of point i at src[i·pstride + c·cstride]) → qpt[n] (xyz, flag:
 // a non-finite query is parked at the target's box corner with flag 1 — the tree never sees a NaN
@@ -433,10 +463,8 @@ struct KnnArgs {
 void launch_knn(hipStream_t s, const TreeView& t, const float4* qpt, const unsigned* qperm, int n, const double* pose,
                 const KnnArgs& a, int lane_mode, int* lists, unsigned* fb_list, unsigned* fb_count, int32_t* idx_out,
                 double* d2_out, int32_t* found_out);
-// list block of n kNN queries: positions [kMaxKL + 1][n] (the last row: worst keys), xref, nref
-// (the traversal's Verlet outputs, unread here), the deferred queries' search caps [n]
-inline size_t knn_list_bytes(int n) { return prevnn_bytes(n) + ((size_t)n * 4 + 255) / 256 * 256; }
-inline float* knn_caps_of(int* lists, int n) { return reinterpret_cast<float*>(reinterpret_cast<char*>(lists) + prevnn_bytes(n)); }
+// list block of n kNN queries (ListBlock; xref / nref: the traversal's Verlet outputs, unread here)
+inline size_t knn_list_bytes(int n) { return ListBlock::bytes(n) + ListBlock::part((size_t)n * 4); }
 constexpr int kKnnChunk = 1 << 18;     // queries per launch sequence of imls_knn (larger sets: consecutive chunks)
 
 constexpr int kStatSkipped = 6;   // nbr_stats slot: lanes whose list was reused without traversal

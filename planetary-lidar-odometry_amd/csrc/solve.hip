@@ -485,7 +485,7 @@ __device__ __forceinline__ void solve_final_body(const Rows& rows, int N, const 
 // the same exact (|r|, row) trim as the chain; the SUMS are associated differently: each thread adds
 // its rows t + k·512 in k order, then block_sum28 — not the chain's 256-row slabs — so every frame of
 // ≤ kSmallRows rows (batched or alone, whichever projection kernels produced its rows) takes this
-// kernel and the projection writes no slabs for it (project.hip).
+// kernel and the projection writes no slabs for it (finish.hip).
 constexpr int kSmallBlock = 512;     // 8 waves: ≤ kSmallPer rows per thread, kept in registers between passes
 constexpr int kSmallPer = kSmallRows / kSmallBlock;
 static_assert(kSmallRows % kSmallBlock == 0, "rows per thread");

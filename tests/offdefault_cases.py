@@ -95,7 +95,7 @@ def case_params(key):
     return PROJECT_CASES[key][0]()
 
 
-# The exact branch of the gate (csrc/project.hip angle_reject below its cosine screens): queries 1 cm
+# The exact branch of the gate (csrc/exact_stage.h angle_reject below its cosine screens): queries 1 cm
 # off a map point along its normal, so that the NN-1 normal is that point's, carrying the same normal
 # (cosine 1 give or take a rounding: acos gives 0, a tiny angle, or NaN for a cosine above 1, and a
 # NaN angle passes), the flipped normal (cosine −1 give or take a rounding), a zero normal (0/0: NaN,

@@ -217,6 +217,20 @@ def test_odd_k_rows(ctx):
         check(ctx.knn(q[:500], k, 3.0, False), oracle("golden500", tgt, q[:500], k, 3.0, 0), k)
 
 
+@pytest.mark.parametrize("k", [9, 16])
+def test_list_size_rung_8_to_16(tctx, k):
+    """8 < k ≤ 16: the list-size rung (list length 20, heap capacity 16) between the ones k = 6 and
+    k = 20 take, at its two ends, in every traversal mode; the map and queries of
+    tests/test_gpu_knn_steps.py (5003 points, 333 queries), against the shared brute force."""
+    import test_gpu_knn_steps as steps
+    cl = steps.build_clouds()
+    tgt6 = synth.soa(cl["tgt"])
+    q = np.ascontiguousarray(synth.soa(cl["spread"])[:3].T, np.float32)
+    tctx.set_target(cl["tgt"])
+    for r, self_ok in ((3.0, True), (np.inf, False)):
+        check(tctx.knn(q, k, r, self_ok), brute(tgt6, q, k, r, self_ok), (k, r, self_ok))
+
+
 def test_strided_queries(ctx):
     """Queries taken from a wider array (stride 6 floats)."""
     tgt, q = golden_pair()

@@ -5,7 +5,7 @@ under that file's contract: validity masks, reject counters, indices, x and n bi
 1e-5 (registrations: iterations, status, per-iteration counts, pose within 1e-6).
 
 (a) 1, 2, 3, 20 and 21 queries within centimetres of one map point: that point's leaf is wanted by
-    exactly that many lanes — odd and even numbers of sparse trips, kSparseLanes (20, project.hip)
+    exactly that many lanes — odd and even numbers of sparse trips, kSparseLanes (20, project_common.h)
     and one past it (the broadcast scan).
 (b) maps of 65, 127, 200 and 257 points at leaf 64: a last leaf of 1 and of 63 points, and
     P = 2, 4, 8 leaves, so the node step descends 1, 2 and 3 levels; K = 8 and the map's own points

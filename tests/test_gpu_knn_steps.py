@@ -8,7 +8,7 @@ y within 1e-5; every query is compared.
 Sizes: a map of 5003 points and sources of 333 / 301 queries — neither a multiple of 64, so the last
 leaf and the last packet are partial — and a few ICP iterations: each case runs in about a second.
 
-Which leaf path runs follows from the queries' layout (kSparseLanes = 20 in project.hip): queries
+Which leaf path runs follows from the queries' layout (kSparseLanes = 20 in project_common.h): queries
 spread over the whole map leave ≤ 20 lanes of a packet wanting any one leaf (the sparse scan);
 a whole packet of queries within a few centimetres of one map point all want that point's leaf
 (the broadcast scan).  The debug-trace build's counts of sparse and broadcast leaf visits for these
@@ -144,6 +144,63 @@ def test_ties_and_duplicates(clouds, K):
         c.set_target(tgt)
         c.set_source(src)
         _check_projection(c.project(np.eye(4)), want)
+
+
+_RUNG_ORACLE = {}
+
+
+def _rung_oracle(clouds, K, src):
+    """The oracle's projection of clouds[src] at the identity with search_number K, once per (K, src)."""
+    if (K, src) not in _RUNG_ORACLE:
+        p = config.bench_params(ITERS)
+        p.search_number = K
+        _RUNG_ORACLE[K, src] = oc.project(synth.soa(clouds[src]), synth.soa(clouds["tgt"]), np.eye(4), p)
+    return _RUNG_ORACLE[K, src]
+
+
+@pytest.mark.parametrize("path", ["packets", "wave_per_query", "fused", "lane"])
+@pytest.mark.parametrize("K", [8, 16, 20, 32])
+def test_list_size_rungs_alone(clouds, K, path):
+    """Every rung of the K → (list length, heap capacity) table (K ≤ 8, ≤ 16, ≤ 20, > 20) on every
+    launch path of a frame alone: packets + k_finish, one wave per query + k_finish (the map itself as
+    the source: 5003 queries, above the fused kernel's 4096), the fused kernel (333 queries), and
+    every query through the exact per-lane kernel.  What this pins is the launch plumbing and the list
+    block's addresses on each path for each instantiation; it does not pin the table's values (a list
+    too short only sends more queries to the exact fallback, which still answers right)."""
+    mode = {"packets": _abi.IMLS_TRAVERSAL_PACKETS, "wave_per_query": _abi.IMLS_TRAVERSAL_WAVE_PER_QUERY,
+            "fused": _abi.IMLS_TRAVERSAL_WAVE_PER_QUERY, "lane": _abi.IMLS_TRAVERSAL_LANE}[path]
+    src = "tgt" if path == "wave_per_query" else "spread"
+    p = config.bench_params(ITERS)
+    p.search_number = K
+    with imls_icp.ImlsContext(p) as c:
+        c.set_option("traversal", mode)
+        c.set_target(clouds["tgt"])
+        c.set_source(clouds[src])
+        _check_projection(c.project(np.eye(4)), _rung_oracle(clouds, K, src))
+
+
+@pytest.mark.parametrize("trav", ["packets", "wave_per_query"])
+@pytest.mark.parametrize("K", [8, 16, 20, 32])
+def test_list_size_rungs_batched(clouds, K, trav):
+    """The same rungs through the batched kernels: two frames in one call, each the oracle's frame."""
+    p = config.bench_params(ITERS)
+    p.search_number = K
+    if K not in _RUNG_ORACLE:   # the oracle's two registrations, once per K
+        _RUNG_ORACLE[K] = [oc.register_frame(synth.soa(clouds[k]), synth.soa(clouds["tgt"]), p) for k in ("reg", "reg2")]
+    want = _RUNG_ORACLE[K]
+    ctxs = [imls_icp.ImlsContext(p) for _ in range(2)]
+    try:
+        for c, k in zip(ctxs, ("reg", "reg2")):
+            c.set_option("traversal", {"packets": _abi.IMLS_TRAVERSAL_PACKETS,
+                                       "wave_per_query": _abi.IMLS_TRAVERSAL_WAVE_PER_QUERY}[trav])
+            c.set_target(clouds["tgt"])
+            c.set_source(clouds[k])
+        poses, iters, status, traces = imls_icp.register_frames(ctxs)
+    finally:
+        for c in ctxs:
+            c.close()
+    for f, o in enumerate(want):
+        _check_frame(dict(pose=poses[f], iters=iters[f], status=status[f], trace=traces[f]), o)
 
 
 @pytest.mark.parametrize("packet", [16, 32])

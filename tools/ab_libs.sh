@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of several libraries (outputs under gpurun_out/${OUT:-ab}/): config B (BENCH_ARGS) for
-# the product library and each csrc/var_NAME/libimls_gpu.so named in VARS, alternated ROUNDS times;
+# the product library and each csrc/var_NAME/libimls_gpu.so (tools/build_full_variant.sh) named in VARS, alternated ROUNDS times;
 # one line per run: pairs/s, busy projection ms per step, one-pair k_knn_wave / k_finish µs.
 set -u
 O=gpurun_out/${OUT:-ab}

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Static instruction counts of the packet-traversal kernels in a gfx950 assembly listing.
 
-    hipcc <product flags> -S --cuda-device-only project.hip -o project.s
-    python tools/asm_counts.py project.s [substring of the mangled kernel name ...]
+    hipcc <product flags> -S --cuda-device-only knn_wave.hip -o knn_wave.s
+    python tools/asm_counts.py knn_wave.s [substring of the mangled kernel name ...]
 
 Per kernel: the resource metadata (VGPRs, SGPRs, spills, LDS), the instruction mix, the lane-spill
 reloads (v_readlane_b32 from the spill VGPRs is not told apart from data readlanes: both counted),

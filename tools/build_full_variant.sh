@@ -1,7 +1,6 @@
 #!/bin/bash
-# Variant library for same-box A/B built from EVERY source with extra flags (a flag that more than
-# one file reads, e.g. -DIMLS_DEBUG_WAVE_TRACE, needs this; a project.hip-only flag can use
-# tools/build_variant.sh): csrc/var_NAME/libimls_gpu.so.
+# Variant library for same-box A/B built from EVERY source with extra flags (the kernels are spread
+# over several units, so a flag must reach all of them): csrc/var_NAME/libimls_gpu.so.
 # usage: tools/build_full_variant.sh NAME [-DFLAG=VALUE ...]
 set -eu
 C=planetary-lidar-odometry_amd/csrc

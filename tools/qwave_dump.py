@@ -25,7 +25,7 @@ for iters in (20, 1):
             c.register_frame()
         n = len(fr[1 - 3 % 2][1])
         buf = np.zeros((n, 16), np.uint32)
-        got = lib.imls_debug_waves(C.c_void_p(buf.ctypes.data), n)
+        got = lib.imls_debug_qwaves(C.c_void_p(buf.ctypes.data), n)
     r = buf[:got].astype(np.int64)
     t0 = r[:, 0].min()
     st, mid, en = (r[:, 0] - t0) / 100.0, (r[:, 1] - t0) / 100.0, (r[:, 2] - t0) / 100.0
