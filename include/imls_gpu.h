@@ -336,8 +336,60 @@ int imls_map_push_posed_device(imls_ctx* ctx, const float* d_soa6, size_t n, con
  * data is the caller's).  An empty FIFO or an identity pose is a no-op. */
 int imls_map_rebase(imls_ctx* ctx, const double pose[16]);
 int imls_map_clear(imls_ctx* ctx);
-/* FIFO entries and their total point count (before the NaN filter). */
+/* FIFO entries and their total point count (before the NaN filter).  While the context holds a voxel
+ * map (below): one entry, the map's points. */
 int imls_map_size(imls_ctx* ctx, size_t* entries, size_t* points);
+
+/* ---- voxel map ---------------------------------------------------------------------------
+ * A second map kind beside the FIFO (no reference equivalent; the local map of KISS-ICP / CT-ICP): an
+ * ordered list of (point, normal) floats in a fixed map frame with at most max_per_voxel points per
+ * voxel of a voxel_size grid, and nothing farther than max_range from the sensor.  A context holds
+ * one map kind at a time: an update on a context whose FIFO holds points, or a FIFO push on a context
+ * whose voxel map holds points, is IMLS_ERR_STATE until imls_map_clear (which empties whichever map
+ * is held).  One update (pose = map ← scan; a non-finite entry in any of the 16 → IMLS_ERR_ARG; the
+ * last row is checked but not used in the arithmetic):
+ *  1. a scan row with a non-finite coordinate, tested as given, is dropped (scan_nonfinite); every
+ *     other row enters the map frame by imls_map_push_posed's arithmetic (an identity pose leaves
+ *     the bits as they are).  A finite row whose map-frame float overflows or is NaN (coordinates
+ *     near FLT_MAX, extreme pose entries) fails the grid test of step 3: scan_out_of_grid;
+ *  2. the candidates are the old map in its stored order, then the scan's surviving rows in order;
+ *  3. a candidate's voxel index is i_a = floor(double(c_a) / double(voxel_size)) per axis, from the
+ *     stored floats; any i_a outside [−2²⁰, 2²⁰ − 1] drops it (*_out_of_grid); its key is
+ *     (i_z + 2²⁰) << 42 | (i_y + 2²⁰) << 21 | (i_x + 2²⁰).  Nothing about voxels is stored;
+ *  4. with t the pose's translation and d = double(c) − t, the candidate stays iff
+ *     (dx·dx + dy·dy) + dz·dz ≤ double(max_range)² (inclusive; +inf keeps everything); dropped old
+ *     rows count map_out_of_range, dropped scan rows scan_out_of_range;
+ *  5. the survivors are ordered by key, ties in candidate order (older first), and the first
+ *     max_per_voxel of each key stay (dropped: map_trimmed — only after a rebase or a parameter
+ *     change — and scan_full);
+ *  6. the survivors in that order are the new map and the context's target, exactly as
+ *     imls_set_target_device on that SoA6 buffer would make them; an empty map means no target.
+ * The update waits once, for the counts.  n_map (nullable) receives the map's size.  IMLS_ERR_STATE
+ * while a registration is pending.  imls_map_rebase transforms the stored floats in place and
+ * re-installs the target (no cap is applied then: the next update trims).  imls_set_target* replaces
+ * the index without touching the map. */
+typedef struct imls_voxel_map_params {
+    float voxel_size;        /* metres; finite, > 0 */
+    int32_t max_per_voxel;   /* ≥ 1 */
+    float max_range;         /* metres from the sensor (the pose's translation); > 0, +inf allowed */
+} imls_voxel_map_params;
+void imls_default_voxel_map_params(imls_voxel_map_params* p);   /* 0.5 m, 20, 100 m */
+typedef struct imls_voxel_map_info {
+    uint64_t points, voxels;             /* the map after the update: rows, distinct keys */
+    uint64_t scan_inserted, scan_nonfinite, scan_out_of_grid, scan_out_of_range, scan_full;   /* sum: the scan's rows */
+    uint64_t map_out_of_grid, map_out_of_range, map_trimmed;   /* old rows dropped */
+} imls_voxel_map_info;
+/* Applies from the next update on (keys are recomputed from the floats at every update). */
+int imls_voxel_map_set_params(imls_ctx* ctx, const imls_voxel_map_params* p);
+int imls_voxel_map_update(imls_ctx* ctx, const float* xyz, const float* nrm, size_t n, size_t stride_floats,
+                          const double pose[16], size_t* n_map);
+/* Device-resident scan (SoA6 floats in HBM, read on the context's stream before the call returns). */
+int imls_voxel_map_update_device(imls_ctx* ctx, const float* d_soa6, size_t n, const double pose[16], size_t* n_map);
+/* The counters of the last update (zeros before the first).  Never launches, never waits. */
+int imls_voxel_map_info_get(imls_ctx* ctx, imls_voxel_map_info* out);
+/* The map as stored, SoA6 [6][*n] floats (for tests, tools, saving).  *n always receives the map's
+ * size; soa6_out may be NULL to ask for it; cap (rows) < *n → IMLS_ERR_CAPACITY. */
+int imls_voxel_map_download(imls_ctx* ctx, float* soa6_out, size_t cap, size_t* n);
 
 /* Tensor voting input (use_tensor_voting): the target's per-point input tensors T — what
  * VoteForAny's tv_input.encode(m_targetPointCloudDP, AWARE_TENSOR) produces (imls_icp.cpp:179,
@@ -848,7 +900,8 @@ int imls_get_option(imls_ctx* ctx, int32_t option, double* value);
  * imls_sample_point_cloud_device (which record 5, 6, 7, 9 and 10 for the kernels they share with
  * the calls above), 12 = the deskew kernel (imls_deskew, imls_deskew_device, and the sweep's after
  * imls_sweep_set_motion), 13 = the pose-info kernels (imls_capture_pose_info; recorded with enable 1
- * only).  enable: 0 off, 1 every kind above (the members of an imls_register_frames batch then build
+ * only), 14 = the voxel-map update (imls_voxel_map_update[_device]: keys, sort, cap and gather; the index
+ * build that follows is kind 1).  enable: 0 off, 1 every kind above (the members of an imls_register_frames batch then build
  * their indices one by one, each inside its events),
  * 2 light — only the projection (0) and solve-chain (2) events of the iterations, the launch
  * sequence otherwise unchanged (for timing a concurrent workload). */

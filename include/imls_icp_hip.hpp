@@ -195,7 +195,26 @@ public:
         detail::check(imls_map_push_posed(ctx_, x, nx, n, n ? stride(*cloud) : 6, pose, &n_map), ctx_);
         return n_map;
     }
-    // every FIFO entry re-expressed under `pose` (new ← old map frame)
+    // The voxel map (imls_gpu.h "voxel map") in place of the FIFO: at most max_per_voxel points per
+    // voxel, nothing farther than max_range from the sensor.  voxelMapUpdate is mapPushPosed's call
+    // for that map (returns the map's size); voxelMapInfo the counters of the last update.
+    void setVoxelMapParams(const imls_voxel_map_params& p) { detail::check(imls_voxel_map_set_params(ctx_, &p), ctx_); }
+    template <class CloudPtr>
+    size_t voxelMapUpdate(const CloudPtr& cloud, const double pose[16]) {
+        size_t n_map = 0;
+        const size_t n = cloud->size();
+        const float* x = n ? &cloud->points[0].x : nullptr;
+        const float* nx = n ? &cloud->points[0].normal_x : nullptr;
+        detail::check(imls_set_params(ctx_, &params_), ctx_);
+        detail::check(imls_voxel_map_update(ctx_, x, nx, n, n ? stride(*cloud) : 6, pose, &n_map), ctx_);
+        return n_map;
+    }
+    imls_voxel_map_info voxelMapInfo() const {
+        imls_voxel_map_info info;
+        detail::check(imls_voxel_map_info_get(ctx_, &info), ctx_);
+        return info;
+    }
+    // the map — every FIFO entry, or the voxel map's points — re-expressed under `pose` (new ← old map frame)
     void mapRebase(const double pose[16]) { detail::check(imls_map_rebase(ctx_, pose), ctx_); }
     // registerFrame starts at rPose = pose (the scan's predicted pose in the map frame); nullptr = I
     void setInitialPose(const double* pose) { detail::check(imls_set_initial_pose(ctx_, pose), ctx_); }

@@ -253,6 +253,27 @@ def default_sweep_params() -> ImlsSweepParams:
     return p
 
 
+class ImlsVoxelMapParams(C.Structure):
+    """imls_voxel_map_params (include/imls_gpu.h): the voxel map's grid, cap and range."""
+    _fields_ = [("voxel_size", C.c_float), ("max_per_voxel", C.c_int32), ("max_range", C.c_float)]
+
+
+def default_voxel_map_params() -> ImlsVoxelMapParams:
+    """0.5 m voxels, 20 points each, 100 m: the values of imls_default_voxel_map_params(), computed here
+    so CPU-only code needs no library (tests/test_voxel_map_model.py compares the two)."""
+    return ImlsVoxelMapParams(0.5, 20, 100.0)
+
+
+class ImlsVoxelMapInfo(C.Structure):
+    """imls_voxel_map_info (include/imls_gpu.h): the counters of one voxel-map update."""
+    _fields_ = [(k, C.c_uint64) for k in (
+        "points", "voxels", "scan_inserted", "scan_nonfinite", "scan_out_of_grid", "scan_out_of_range", "scan_full",
+        "map_out_of_grid", "map_out_of_range", "map_trimmed")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class ImlsPairInput(C.Structure):
     """imls_pair_input (include/imls_gpu.h)."""
     _fields_ = [("src_xyz", C.c_void_p), ("src_nrm", C.c_void_p), ("n_src", C.c_size_t),
@@ -344,6 +365,12 @@ def _bind(lib: C.CDLL, strict: bool = True) -> C.CDLL:
         "imls_sweep_set_motion": (C.c_int, [VP, VP, C.c_int32]),
         "imls_capture_pose_info": (C.c_int, [VP, C.c_int]),
         "imls_pose_info": (C.c_int, [VP, P(ImlsPoseInfo)]),
+        "imls_default_voxel_map_params": (None, [P(ImlsVoxelMapParams)]),
+        "imls_voxel_map_set_params": (C.c_int, [VP, P(ImlsVoxelMapParams)]),
+        "imls_voxel_map_update": (C.c_int, [VP, VP, VP, SZ, SZ, VP, P(SZ)]),
+        "imls_voxel_map_update_device": (C.c_int, [VP, VP, SZ, VP, P(SZ)]),
+        "imls_voxel_map_info_get": (C.c_int, [VP, P(ImlsVoxelMapInfo)]),
+        "imls_voxel_map_download": (C.c_int, [VP, VP, SZ, P(SZ)]),
     }
     for name, (res, args) in sig.items():
         if not strict and not hasattr(lib, name):
@@ -374,6 +401,8 @@ ABI_SYMBOLS = (
     "imls_default_sweep_params", "imls_sweep_process", "imls_sweep_process_device", "imls_sweep_reset",
     "imls_sweep_clouds_device", "imls_sweep_download", "imls_sample_point_cloud_device", "imls_shuffle_positions",
     "imls_deskew", "imls_deskew_device", "imls_sweep_set_motion", "imls_capture_pose_info", "imls_pose_info",
+    "imls_default_voxel_map_params", "imls_voxel_map_set_params", "imls_voxel_map_update", "imls_voxel_map_update_device",
+    "imls_voxel_map_info_get", "imls_voxel_map_download",
 )
 
 _LIB = None

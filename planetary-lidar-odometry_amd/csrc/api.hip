@@ -700,6 +700,9 @@ void imls_destroy(imls_ctx* c) {
     if (c->h_fifo_cnt) (void)hipHostFree(c->h_fifo_cnt);
     if (c->h_fifo_clamp) (void)hipHostFree(c->h_fifo_clamp);
     if (c->ev_fifo) (void)hipEventDestroy(c->ev_fifo);
+    for (DevBuf* b : {&c->vox.buf[0], &c->vox.buf[1], &c->vox.scan, &c->vox.scratch}) if (b->p) (void)hipFree(b->p);
+    if (c->vox.h_rec) (void)hipHostFree(c->vox.h_rec);
+    if (c->vox.ev) (void)hipEventDestroy(c->vox.ev);
     if (c->macc.p) (void)hipFree(c->macc.p);
     if (c->skept.p) (void)hipFree(c->skept.p);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);

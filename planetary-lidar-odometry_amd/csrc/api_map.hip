@@ -215,6 +215,7 @@ static int map_assemble(imls_ctx* c, size_t* n_map) {
 static int map_push(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, const float* d_soa6,
                     size_t* n_map, const Pose12* pose = nullptr) {
     if (n > (size_t)0x7fffffff) return fail(c, IMLS_ERR_ARG, "scan too large");
+    if (c->vox.n > 0) return fail(c, IMLS_ERR_STATE, "the context holds a voxel map: imls_map_clear first");
     // max_queue_size 1 with a device scan (the shipped config, device frames): the map IS this
     // scan, dropped at the next push — index it where it lies (its NaN filter reads it on this
     // stream, as the slot copy would), no FIFO copy.  (A posed scan needs its transformed copy.)
@@ -346,6 +347,11 @@ int imls_map_rebase(imls_ctx* c, const double pose[16]) {
     if (!pose || !read_pose(pose, &P, &identity)) return fail(c, IMLS_ERR_ARG, "map pose: null or non-finite entry");
     if (c->pending || c->batch_member) return fail(c, IMLS_ERR_STATE, "a registration is pending: collect its result first");
     if (int rc = check_device(c)) return rc;
+    if (!identity && c->vox.n > 0) {      // the voxel map: its stored floats in place, the target re-installed
+        if (int rc = pose_soa6(c->stream, (const float*)c->vox.buf[c->vox.cur].p, (float*)c->vox.buf[c->vox.cur].p, c->vox.n, P, c->err))
+            return rc;
+        return do_set_target(c, (const float*)c->vox.buf[c->vox.cur].p, c->vox.n, nullptr);
+    }
     if (identity || c->map_points == 0) return IMLS_OK;
     for (const auto& e : c->fifo)
         if (e.ghost && e.n > 0)
@@ -387,13 +393,126 @@ int imls_map_clear(imls_ctx* c) {
     c->merged_ids.clear();
     c->m_n = 0;
     c->fq_valid = false;
+    c->vox.n = 0;
     return IMLS_OK;
 }
 
 int imls_map_size(imls_ctx* c, size_t* entries, size_t* points) {
     if (!c) return IMLS_ERR_ARG;
-    if (entries) *entries = c->fifo.size();
-    if (points) *points = c->map_points;
+    if (entries) *entries = c->vox.n > 0 ? 1 : c->fifo.size();
+    if (points) *points = c->vox.n > 0 ? c->vox.n : c->map_points;
+    return IMLS_OK;
+}
+
+// ---- voxel map (include/imls_gpu.h "voxel map"; kernels in voxel_map.hip) ---------------------------
+void imls_default_voxel_map_params(imls_voxel_map_params* p) {
+    if (!p) return;
+    p->voxel_size = 0.5f;
+    p->max_per_voxel = 20;
+    p->max_range = 100.0f;
+}
+
+int imls_voxel_map_set_params(imls_ctx* c, const imls_voxel_map_params* p) {
+    if (!c || !p) return IMLS_ERR_ARG;
+    if (!std::isfinite(p->voxel_size) || !(p->voxel_size > 0.f)) return fail(c, IMLS_ERR_ARG, "voxel_size must be finite and > 0");
+    if (p->max_per_voxel < 1) return fail(c, IMLS_ERR_ARG, "max_per_voxel must be >= 1");
+    if (!(p->max_range > 0.f)) return fail(c, IMLS_ERR_ARG, "max_range must be > 0 (+inf allowed)");
+    c->vox.P = *p;
+    return IMLS_OK;
+}
+
+// One update: the scan to its staging buffer (a host scan: uploaded there and transformed in place),
+// the merge into the other map buffer, one wait for the record, the new map installed as the target.
+static int voxel_update(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, const float* d_soa6,
+                        const double pose[16], size_t* n_map) {
+    auto& v = c->vox;
+    VoxelGrid G{};
+    bool identity = false;
+    if (!pose || !read_pose(pose, &G.P, &identity)) return fail(c, IMLS_ERR_ARG, "map pose: null or non-finite entry");
+    if (n > (size_t)0x7fffffff || v.n + n > (size_t)0x7fffffff) return fail(c, IMLS_ERR_ARG, "scan too large");
+    if (c->pending || c->batch_member) return fail(c, IMLS_ERR_STATE, "a registration is pending: collect its result first");
+    // (points on both sides: map_push tests vox.n; a FIFO of empty scans holds nothing)
+    if (c->map_points > 0) return fail(c, IMLS_ERR_STATE, "the context holds a map FIFO: imls_map_clear first");
+    if (int rc = check_device(c)) return rc;
+    G.identity = identity ? 1 : 0;
+    G.voxel = (double)v.P.voxel_size;
+    G.r2 = (double)v.P.max_range * (double)v.P.max_range;
+    G.cap = (unsigned long long)v.P.max_per_voxel;
+    if (!v.h_rec && hipHostMalloc((void**)&v.h_rec, kVoxRecWords * sizeof(unsigned)) != hipSuccess)
+        return fail(c, IMLS_ERR_DEVICE, "hipHostMalloc (voxel map)");
+    if (!v.ev && hipEventCreateWithFlags(&v.ev, hipEventDisableTiming) != hipSuccess) return fail(c, IMLS_ERR_DEVICE, "hipEventCreate");
+    const size_t n_old = v.n, total = n_old + n;
+    const float* scan_in = d_soa6;
+    if (n > 0 && !d_soa6) {
+        if (int rc = upload_soa6(c, v.scan, xyz, nrm, n, stride, 0)) return rc;
+        scan_in = (const float*)v.scan.p;
+    } else if (n > 0 && !grow(v.scan, n * 24)) {
+        return fail(c, IMLS_ERR_DEVICE, "hipMalloc (voxel map scan)");
+    }
+    if (total > 0 && !grow(v.buf[v.cur ^ 1], total * 24)) return fail(c, IMLS_ERR_DEVICE, "hipMalloc (voxel map)");
+    int slot = -1;
+    timed_begin(c, kTimeVoxelMap, slot);
+    const int rc = voxel_map_merge(c->stream, (const float*)v.buf[v.cur].p, n_old, scan_in, (float*)v.scan.p, n, G,
+                                   (float*)v.buf[v.cur ^ 1].p, v.scratch, v.h_rec, c->err);
+    timed_end(c, kTimeVoxelMap, slot);
+    if (rc) return rc;
+    if (hipEventRecord(v.ev, c->stream) != hipSuccess || hipEventSynchronize(v.ev) != hipSuccess)
+        return fail(c, IMLS_ERR_DEVICE, "voxel map update failed");
+    c->stage_pending[0] = false;          // the stream has passed every reader of an uploaded scan
+    const unsigned* r = v.h_rec;
+    imls_voxel_map_info& I = v.info;
+    I.points = r[kVoxKept];
+    I.voxels = r[kVoxVoxels];
+    I.scan_nonfinite = r[kVoxScanNonfinite];
+    I.scan_out_of_grid = r[kVoxScanGrid];
+    I.scan_out_of_range = r[kVoxScanRange];
+    I.scan_full = r[kVoxScanFull];
+    I.map_out_of_grid = r[kVoxMapGrid];
+    I.map_out_of_range = r[kVoxMapRange];
+    I.map_trimmed = r[kVoxMapTrimmed];
+    I.scan_inserted = (uint64_t)n - I.scan_nonfinite - I.scan_out_of_grid - I.scan_out_of_range - I.scan_full;
+    v.cur ^= 1;
+    v.n = (size_t)I.points;
+    if (n_map) *n_map = v.n;
+    if (v.n == 0) {                       // an empty map: no target (as map_assemble's M = 0)
+        c->tgt_pending = false;
+        c->has_target = false;
+        c->has_corr = false;
+        c->fifo_inc = false;
+        c->M = 0;
+        return IMLS_OK;
+    }
+    // (every stored point is finite, so the target's NaN filter keeps them all: no second wait for its count)
+    return do_set_target(c, (const float*)v.buf[v.cur].p, v.n, nullptr);
+}
+
+int imls_voxel_map_update(imls_ctx* c, const float* xyz, const float* nrm, size_t n, size_t stride, const double pose[16],
+                          size_t* n_map) {
+    if (!c) return IMLS_ERR_ARG;
+    if (n > 0 && (!xyz || !nrm || stride < 3)) return fail(c, IMLS_ERR_ARG, "bad cloud pointer/stride");
+    return voxel_update(c, xyz, nrm, n, stride, nullptr, pose, n_map);
+}
+
+int imls_voxel_map_update_device(imls_ctx* c, const float* d_soa6, size_t n, const double pose[16], size_t* n_map) {
+    if (!c || (n > 0 && !d_soa6)) return IMLS_ERR_ARG;
+    return voxel_update(c, nullptr, nullptr, n, 0, d_soa6, pose, n_map);
+}
+
+int imls_voxel_map_info_get(imls_ctx* c, imls_voxel_map_info* out) {
+    if (!c || !out) return IMLS_ERR_ARG;
+    *out = c->vox.info;
+    return IMLS_OK;
+}
+
+int imls_voxel_map_download(imls_ctx* c, float* soa6_out, size_t cap, size_t* n) {
+    if (!c || !n) return IMLS_ERR_ARG;
+    *n = c->vox.n;
+    if (!soa6_out || c->vox.n == 0) return IMLS_OK;
+    if (cap < c->vox.n) return fail(c, IMLS_ERR_CAPACITY, "voxel map download: buffer too small");
+    if (int rc = check_device(c)) return rc;
+    if (hipMemcpyAsync(soa6_out, c->vox.buf[c->vox.cur].p, c->vox.n * 24, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(c, IMLS_ERR_DEVICE, "voxel map download failed");
     return IMLS_OK;
 }
 

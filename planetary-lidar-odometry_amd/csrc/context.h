@@ -82,6 +82,18 @@ struct imls_ctx {
     hipEvent_t ev_fifo = nullptr;         // after the last incremental build (batch joins)
     DevBuf macc;
     size_t map_points = 0;                // Σ n over the FIFO (before the NaN filter)
+    // voxel map (imls_voxel_map_update, voxel_map.hip): the map as SoA6 [6][n] in buf[cur], the other
+    // buffer the next update's output; the scan's map-frame copy; the update's scratch; the pinned
+    // record the one wait of an update reads.  A context holds this map or the FIFO, never both.
+    struct VoxelMap {
+        DevBuf buf[2], scan, scratch;
+        int cur = 0;
+        size_t n = 0;
+        imls_voxel_map_params P{0.5f, 20, 100.0f};
+        imls_voxel_map_info info{};
+        unsigned* h_rec = nullptr;
+        hipEvent_t ev = nullptr;
+    } vox;
     DevBuf fb;                            // deferred-query counts per k_finish block + their lists
     size_t fb_off = 64;                   // words: start of the lists in fb
     DevBuf lkeys;                         // leaf first Morton keys + quantisation (seed search)

@@ -52,25 +52,6 @@ __global__ void k_compact(const float* __restrict__ soa, size_t n, const unsigne
     if (kept_index) kept_index[o] = (unsigned)i;
 }
 
-// float(P·[p;1]) and float(R·n) in transform_query's arithmetic (geom.h): double products summed in
-// order, no contraction (the build's -ffp-contract=off), one rounding to float per component.
-__device__ __forceinline__ void pose_point(const Pose12& P, float x, float y, float z, float nx, float ny, float nz,
-                                           float o[3], float on[3]) {
-    const double pd[3] = {x, y, z}, nd[3] = {nx, ny, nz};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double v = P.T[r * 4 + 0] * pd[0];
-        v = v + P.T[r * 4 + 1] * pd[1];
-        v = v + P.T[r * 4 + 2] * pd[2];
-        v = v + P.T[r * 4 + 3] * 1.0;
-        o[r] = (float)v;
-        double w = P.T[r * 4 + 0] * nd[0];
-        w = w + P.T[r * 4 + 1] * nd[1];
-        w = w + P.T[r * 4 + 2] * nd[2];
-        on[r] = (float)w;
-    }
-}
-
 // k_compact for a posed map push: the same scatter, each kept point written in the map frame.  The
 // pose is a launch argument (constant address space: scalar loads, wave-uniform).
 __global__ void k_compact_posed(const float* __restrict__ soa, size_t n, const unsigned* __restrict__ flag,

@@ -311,6 +311,25 @@ __device__ __forceinline__ PairDev device_view(const PairDev* pa) {
 // A rigid pose (rows 0-2 of the row-major 4×4) handed to a kernel by value: launch arguments live in
 // the constant address space, so a wave reads it with one set of scalar loads (as transform_query's).
 struct Pose12 { double T[12]; };
+// float(P·[p;1]) and float(R·n) in transform_query's arithmetic (geom.h): double products summed in
+// order, no contraction (the build's -ffp-contract=off), one rounding to float per component.
+__device__ __forceinline__ void pose_point(const Pose12& P, float x, float y, float z, float nx, float ny, float nz,
+                                           float o[3], float on[3]) {
+    const double pd[3] = {x, y, z}, nd[3] = {nx, ny, nz};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double v = P.T[r * 4 + 0] * pd[0];
+        v = v + P.T[r * 4 + 1] * pd[1];
+        v = v + P.T[r * 4 + 2] * pd[2];
+        v = v + P.T[r * 4 + 3] * 1.0;
+        o[r] = (float)v;
+        double w = P.T[r * 4 + 0] * nd[0];
+        w = w + P.T[r * 4 + 1] * nd[1];
+        w = w + P.T[r * 4 + 2] * nd[2];
+        on[r] = (float)w;
+    }
+}
+
 // `pose` (nullable): the posed map push — a kept point leaves the scatter pass as float(pose·[p;1])
 // and its normal rotated, in transform_query's arithmetic (geom.h); the filter tests the point as given.
 int filter_async(hipStream_t s, const float* d_soa6, size_t n_in, DevBuf& pt, DevBuf& nr, DevBuf& scratch,
@@ -393,6 +412,27 @@ int fifo_merge(hipStream_t s, const unsigned long long* a, const unsigned* av, i
 int fifo_index(hipStream_t s, const unsigned long long* mkey, const unsigned* mval, int M, const FifoRunTable& runs,
                const float* fq, const unsigned* clamp, unsigned* h_clamp, int B, DevBuf& lkeys, DevBuf& mpt, DevBuf& nodes,
                DevBuf& treescratch, int* P_out, int* levels_out, std::string& err);
+
+// voxel_map.hip — the voxel map's update (imls_voxel_map_update): candidates = the old
+// map's rows then the scan's, one 64-bit voxel key each from the stored floats, a stable radix sort,
+// the first `cap` rows of every key kept, gathered in that order into `out`.
+struct VoxelGrid {                     // by value in the launches, as Pose12
+    Pose12 P;                          // map ← scan
+    double voxel;                      // double(voxel_size)
+    double r2;                         // double(max_range)², +inf: no range test drops anything
+    unsigned long long cap;            // max_per_voxel
+    int identity;                      // the pose is exactly I: scan rows keep their bits
+};
+// the update's record, device and pinned host copy: words of VoxelRec
+enum VoxelRec {
+    kVoxKept = 0, kVoxVoxels, kVoxScanNonfinite, kVoxScanGrid, kVoxScanRange, kVoxScanFull, kVoxMapGrid, kVoxMapRange,
+    kVoxMapTrimmed, kVoxRecWords = 16
+};
+// map: SoA6 [6][n_old]; scan_in: SoA6 [6][n] in the scan frame; scan_out: [6][n], receives the scan in
+// the map frame (may be scan_in); out: ≥ 6·(n_old + n) floats, receives the new map as SoA6 [6][kept].
+// h_rec (pinned, kVoxRecWords words) is valid once the stream has passed the call.
+int voxel_map_merge(hipStream_t s, const float* map, size_t n_old, const float* scan_in, float* scan_out, size_t n,
+                    const VoxelGrid& g, float* out, DevBuf& scratch, unsigned* h_rec, std::string& err);
 
 // project.hip
 // k_knn_wave → k_finish (+ the exact k_project_lane fallback for uncertified queries); lane_mode
@@ -685,7 +725,8 @@ enum TimingKind {
     kTimeSweep = 11,      // sweep sampler / compaction / cloud assembly (recorded by sweep.hip)
     kTimeDeskew = 12,     // deskew kernel
     kTimePoseInfo = 13,   // pose-info kernels (k_info_rows, k_info_final)
-    kTimingKinds = 14
+    kTimeVoxelMap = 14,   // voxel-map update (keys, sort, cap, gather)
+    kTimingKinds = 15
 };
 // timing hook of the caller: a pair of events that will be harvested as `kind`, or false (timing off)
 typedef bool (*SweepMark)(void* owner, int kind, hipEvent_t ev[2]);

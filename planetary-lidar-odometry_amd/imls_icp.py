@@ -219,6 +219,54 @@ class ImlsContext:
         self._check(self.lib.imls_map_size(self.ctx, C.byref(e), C.byref(p)))
         return e.value, p.value
 
+    # -- voxel map (imls_voxel_map_*: a density-capped, range-bounded map in a fixed frame) ------------
+    def set_voxel_map_params(self, params=None, **kw):
+        """The grid, cap and range of the voxel map from the next update on: an ImlsVoxelMapParams, or
+        the defaults (0.5 m, 20, 100 m) with voxel_size= / max_per_voxel= / max_range= overrides."""
+        p = _abi.default_voxel_map_params() if params is None else params
+        if kw:
+            p = _abi.ImlsVoxelMapParams(p.voxel_size, p.max_per_voxel, p.max_range)
+            for k, val in kw.items():
+                if k not in ("voxel_size", "max_per_voxel", "max_range"):
+                    raise TypeError(f"unknown voxel map parameter {k!r}")
+                setattr(p, k, val)
+        self._check(self.lib.imls_voxel_map_set_params(self.ctx, C.byref(p)))
+        self.voxel_map_params = p
+
+    def voxel_map_update(self, cloud, pose=None):
+        """One update of the voxel map with `cloud` at pose (4×4, map ← scan; None = identity): the map
+        becomes the target.  Returns the map's size (imls_voxel_map_update)."""
+        _keep, px, pn, m, stride = _cloud_args(cloud)
+        if m == 0:
+            px, pn, stride = None, None, 6
+        n = C.c_size_t()
+        T = _pose16(np.eye(4) if pose is None else pose)
+        self._check(self.lib.imls_voxel_map_update(self.ctx, px, pn, m, stride, _ptr(T), C.byref(n)))
+        self.n_target = n.value
+        return self.n_target
+
+    def voxel_map_update_device(self, soa6_ptr: int, n: int, pose=None):
+        k = C.c_size_t()
+        T = _pose16(np.eye(4) if pose is None else pose)
+        self._check(self.lib.imls_voxel_map_update_device(self.ctx, C.c_void_p(soa6_ptr), n, _ptr(T), C.byref(k)))
+        self.n_target = k.value
+        return self.n_target
+
+    def voxel_map_info(self) -> dict:
+        """The counters of the last update (imls_voxel_map_info_get): never launches or waits."""
+        info = _abi.ImlsVoxelMapInfo()
+        self._check(self.lib.imls_voxel_map_info_get(self.ctx, C.byref(info)))
+        return info.as_dict()
+
+    def voxel_map_download(self) -> np.ndarray:
+        """The map as stored: (6, n) float32 rows x y z nx ny nz (imls_voxel_map_download)."""
+        n = C.c_size_t()
+        self._check(self.lib.imls_voxel_map_download(self.ctx, None, 0, C.byref(n)))
+        out = np.zeros((6, n.value), np.float32)
+        if n.value:
+            self._check(self.lib.imls_voxel_map_download(self.ctx, _ptr(out), n.value, C.byref(n)))
+        return out
+
     # -- RANSAC rand() stream ---------------------------------------------------------------------
     def seed_rng(self, seed: int):
         self._check(self.lib.imls_seed_rng(self.ctx, int(seed)))
@@ -947,7 +995,12 @@ class LaserOdometry:
     I) so float map coordinates stay near the sensor.  A frame that does not register keeps T_A and
     reports rPose = I.  With max_queue_size 1 the anchor is always the newest scan (pushed as it is,
     the pipelined path kept).  motion_prior "constant_velocity" starts frame k at T_A·(last rPose)
-    instead of T_A (either map model).  In "compensated" mode the trace's poses (and the
+    instead of T_A (any map model).  "voxel" replaces the FIFO by the voxel map (ImlsContext.voxel_map_update,
+    parameters `voxel_map`: an ImlsVoxelMapParams, default 0.5 m / 20 per voxel / 100 m): at most
+    max_per_voxel points per voxel, nothing farther than max_range from the sensor, older points kept
+    first.  It follows "compensated" in every respect (anchor pose, rebase, motion prior, deskew,
+    pose_info) except that it is active for every max_queue_size (which it ignores), is never pipelined,
+    and the push is the update with pose T_A'; `.map_infos` keeps each update's counters.  In "compensated" mode the trace's poses (and the
     imls_iter_results.txt of output_dir) are poses in the map frame.
 
     deskew (process_sweep only; either map model, either motion prior): "none" (default) leaves every
@@ -979,7 +1032,7 @@ class LaserOdometry:
     def __init__(self, params: Optional[_abi.ImlsParams] = None, device: int = 0, pose_file: Optional[str] = None,
                  output_dir: Optional[str] = None, pipelined: Optional[bool] = None, map_model: str = "raw",
                  motion_prior: str = "none", rebase_distance: float = 100.0, producer=None, deskew: str = "none",
-                 initial_motion=None, pose_info: bool = False):
+                 initial_motion=None, pose_info: bool = False, voxel_map=None):
         self.producer = producer        # a producer.ScanRegistration: process_sweep's raw sweep → device clouds
         self.last_sweep = None
         if deskew not in ("none", "constant_velocity"):
@@ -988,8 +1041,10 @@ class LaserOdometry:
         self.initial_motion = None if initial_motion is None else np.array(initial_motion, dtype=np.float64).reshape(4, 4)
         self.motions: list = []         # the motion each process_sweep deskewed with (None: none)
         self._registered = False        # a frame has registered: last_rpose is a measured motion
-        if map_model not in ("raw", "compensated"):
-            raise ValueError('map_model: "raw" or "compensated"')
+        if map_model not in ("raw", "compensated", "voxel"):
+            raise ValueError('map_model: "raw", "compensated" or "voxel"')
+        if map_model == "voxel" and pipelined:
+            raise ValueError('map_model "voxel" is never pipelined: one context holds the map')
         if motion_prior not in ("none", "constant_velocity"):
             raise ValueError('motion_prior: "none" or "constant_velocity"')
         self.map_model = map_model
@@ -1007,6 +1062,9 @@ class LaserOdometry:
         # the same scan); the RANSAC rand() stream is handed from one context to the other, so the
         # draws continue as in one context (tests/test_gpu_stream.py: poses bit-equal to one context)
         self._ctxs = [self.ctx]
+        if map_model == "voxel":
+            pipelined = False               # one context holds the map: the update follows the registration
+            self.ctx.set_voxel_map_params(voxel_map)
         if pipelined is None:
             pipelined = self.ctx.params.max_queue_size == 1
         if pipelined and self.ctx.params.max_queue_size == 1:
@@ -1026,6 +1084,7 @@ class LaserOdometry:
         if self.pose_info:
             for c in self._ctxs:
                 c.capture_pose_info(True)
+        self.map_infos: list = []       # "voxel": the counters of each update (ImlsContext.voxel_map_info)
         self.infos: list = []           # pose_info: the report of each registered frame (or None)
         self.pose_covariances: list = []   # pose_info: the chained 6×6 covariance of each nowPose
         self.covariance_gaps: list = []    # pose_info: indices into infos of the frames that added nothing
@@ -1062,8 +1121,11 @@ class LaserOdometry:
         self.close()
 
     def process(self, filtered_cloud, flat_cloud, timestamp: str = ""):
-        return self._frame(len(flat_cloud), lambda ctx: ctx.set_source(flat_cloud, count=False),
-                           lambda ctx, pose: ctx.map_push(filtered_cloud, pose=pose), timestamp)
+        if self.map_model == "voxel":
+            push = lambda ctx, pose: ctx.voxel_map_update(filtered_cloud, pose)
+        else:
+            push = lambda ctx, pose: ctx.map_push(filtered_cloud, pose=pose)
+        return self._frame(len(flat_cloud), lambda ctx: ctx.set_source(flat_cloud, count=False), push, timestamp)
 
     def sweep_motion(self, motion=None):
         """The motion the next sweep is deskewed with (the class doc's rule), or None."""
@@ -1084,8 +1146,11 @@ class LaserOdometry:
         m = self.sweep_motion(motion)
         self.motions.append(m)
         h = self.last_sweep = self.producer.process_raw_device(raw, front_params, motion=m)
-        return self._frame(h.n_flat, lambda ctx: ctx.set_source_device(h.flat, h.n_flat, count=False),
-                           lambda ctx, pose: ctx.map_push_device(h.filtered, h.n_filtered, pose=pose), timestamp)
+        if self.map_model == "voxel":
+            push = lambda ctx, pose: ctx.voxel_map_update_device(h.filtered, h.n_filtered, pose)
+        else:
+            push = lambda ctx, pose: ctx.map_push_device(h.filtered, h.n_filtered, pose=pose)
+        return self._frame(h.n_flat, lambda ctx: ctx.set_source_device(h.flat, h.n_flat, count=False), push, timestamp)
 
     def _frame(self, n_flat: int, set_source, map_push, timestamp: str = ""):
         """One frame: set_source(ctx) loads the flat cloud, map_push(ctx, pose) pushes the filtered one."""
@@ -1099,7 +1164,7 @@ class LaserOdometry:
         pushed = False
         registers = self.frame_count != 0 and n_flat != 0 and ctx.n_target != 0
         # scan-to-model: the map lives in a fixed frame, this frame starts at its predicted pose in it
-        posed = self.map_model == "compensated" and ctx.params.max_queue_size > 1
+        posed = self.map_model == "voxel" or (self.map_model == "compensated" and ctx.params.max_queue_size > 1)
         predicted = self.motion_prior == "constant_velocity"
         if registers and (posed or predicted):
             ctx.set_initial_pose(chain_pose(self.anchor_pose, self.last_rpose) if predicted else self.anchor_pose)
@@ -1160,6 +1225,8 @@ class LaserOdometry:
                 times.step("2. Matching and solving in flat points")
         if not pushed:
             map_push(nxt, self.anchor_pose if posed else None)
+            if self.map_model == "voxel":
+                self.map_infos.append(nxt.voxel_map_info())
             if posed and float(np.linalg.norm(self.anchor_pose[:3, 3])) > self.rebase_distance:
                 nxt.map_rebase(inv_pose(self.anchor_pose))
                 self.anchor_pose = np.eye(4)

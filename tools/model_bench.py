@@ -12,7 +12,13 @@ synchronous); the index build's device time per push from imls_kernel_timing kin
 second pass with the timing events on: they change the launch sequence, so that pass gives no
 frames/s); ICP iterations per frame; the trajectory RMSE against the generator's ground truth.
 Prints one JSON line.  No threshold: the expectation is the same incremental index cost for both
-models and nothing measurable for the fused transform."""
+models and nothing measurable for the fused transform.
+
+    python tools/model_bench.py --map-model {voxel,compensated,raw} [--frames 12] [--queue 10] [--out FILE.json]
+
+One model alone in the process ("voxel": the voxel map, which ignores --queue): per frame the wall time
+of process(), the device time of the map's update (imls_kernel_timing kind 14) and of the index build
+(kind 1), and the map's size."""
 import argparse
 import json
 import pathlib
@@ -34,6 +40,8 @@ def main():
     ap.add_argument("--flat", type=int, default=2000)
     ap.add_argument("--model", default="hdl64", choices=["hdl64", "vlp16"])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--map-model", default=None, choices=["raw", "compensated", "voxel"],
+                    help="one model alone, per frame: update (kind 14), index (kind 1) and frame time, map size")
     a = ap.parse_args()
 
     import torch                       # first: the process's HIP runtime (as bench.py)
@@ -81,6 +89,47 @@ def main():
         return dict(fps=len(frames) / wall, push_ms=statistics.median(push_ms[1:]), iters=iters,
                     index_ms=index[0] / max(index[1], 1), index_builds=int(index[1]),
                     rmse=float(np.sqrt(np.mean(np.square(err)))))
+
+    def per_frame(model):
+        """One model alone: per frame the wall time of process() (timing off), and in a second pass with
+        the timing events on the device time of the map's update (kind 14, the voxel map only) and of the
+        index build (kind 1) of that frame's push — both are harvested by the next frame's registration,
+        so the last frame's push is not reported — and the map's size after the frame."""
+        out = {}
+        for timing in (False, False, True):        # the first pass warms up
+            wall, sizes, cum = [], [], []
+            with imls_icp.LaserOdometry(p, device=0, map_model=model) as lo:
+                ctx = lo.ctx
+                if timing:
+                    ctx.enable_timing(1)
+                    ctx.reset_timing()
+                for filtered, flat in frames:
+                    t = time.perf_counter()
+                    lo.process(filtered, flat)
+                    wall.append((time.perf_counter() - t) * 1e3)
+                    sizes.append(int(ctx.n_target or 0))
+                    cum.append((ctx.kernel_timing(14)[0], ctx.kernel_timing(1)[0]))
+                err = [np.linalg.norm(now[:3, 3] - truth[k + 1][:3, 3]) for k, (_, now) in enumerate(lo.poses)]
+                infos = list(lo.map_infos)
+            if not timing:
+                out.update(frame_ms=[round(w, 3) for w in wall], map_points=sizes,
+                           rmse_m=round(float(np.sqrt(np.mean(np.square(err)))), 5))
+                if infos:
+                    out["voxels"] = [i["voxels"] for i in infos]
+            else:
+                d = np.diff(np.asarray([(0.0, 0.0)] + cum), axis=0)[1:]
+                out.update(update_ms=[round(float(v), 4) for v in d[:, 0]], index_ms=[round(float(v), 4) for v in d[:, 1]])
+        return out
+
+    if a.map_model:
+        res = dict(tool="model_bench", map_model=a.map_model, sensor=a.model, frames=a.frames, queue=a.queue,
+                   flat_points=a.flat, scan_points=int(np.mean([len(s) for s in scans])), **per_frame(a.map_model))
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+            pathlib.Path(a.out).write_text(line + "\n")
+        return
 
     models = ("raw", "compensated")
     for m in models:                   # warm-up: buffers grown, code objects loaded
