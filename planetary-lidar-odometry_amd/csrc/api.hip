@@ -127,7 +127,7 @@ int check_params(imls_ctx* c, const imls_params* p) {
         if (!(p->tensor_sigma > 0)) return fail(c, IMLS_ERR_ARG, "tensor_voting.sigma must be > 0");
     }
     if (!p->get_normals && p->recompute_normal_count_mode && (p->search_number_normal < 1 || p->search_number_normal > 32))
-        return fail(c, IMLS_ERR_UNSUPPORTED, "search_number_normal must be in [1, 32]");
+        return fail(c, IMLS_ERR_ARG, "search_number_normal must be in [1, 32]");
     if (p->solve_method != IMLS_SOLVE_LS && p->solve_method != IMLS_SOLVE_WEIGHTED_LS && p->solve_method != IMLS_SOLVE_RANSAC)
         return fail(c, IMLS_ERR_UNSUPPORTED, "solve_method must be LS, Weighted LS or RANSAC (Ceres/ICP/Teaser stay on the CPU path)");
     if (p->solve_method == IMLS_SOLVE_RANSAC) {

@@ -348,10 +348,10 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         const bool need_nrm = !c->P.get_normals && c->P.recompute_normal_count_mode &&
                               !(c->rnr_valid && c->rnr_k == c->P.search_number_normal && c->rnr_r == c->P.r_normal);
         if (need_nrm) {
+            // (valid only once the launch below has been issued: a later member's failed check returns
+            // before it, and this member's next use must then compute them)
+            c->rnr_valid = false;
             if (!grow(c->rnr, (size_t)std::max(c->M, 1) * 16)) return fail(L, IMLS_ERR_DEVICE, "hipMalloc (normals)");
-            c->rnr_valid = true;
-            c->rnr_k = c->P.search_number_normal;
-            c->rnr_r = c->P.r_normal;
             any_nrm = true;
             max_m = std::max(max_m, c->M);
         }
@@ -378,6 +378,12 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
     k_batch_init<<<(unsigned)n, 64, 0, s>>>(tab, iters, reinterpret_cast<const double*>(tab + n));
     if (any_nrm && launch_map_normals_batch(s, tab, (int)n, max_m, L->P.search_number_normal, L->P.r_normal))
         return fail(L, IMLS_ERR_DEVICE, "batched map normal launch failed");
+    for (size_t k = 0; k < n; ++k) {
+        if (!L->tab_h[k].recompute_normals) continue;
+        ctxs[k]->rnr_valid = true;
+        ctxs[k]->rnr_k = ctxs[k]->P.search_number_normal;
+        ctxs[k]->rnr_r = ctxs[k]->P.r_normal;
+    }
     const KParams kp = L->kp;
     const RansacParams rp = ransac_params(L->P);
     const int* nh = L->member_n.data();
