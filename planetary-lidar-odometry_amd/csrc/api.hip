@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "context.h"
+#include "index.h"
 
 using namespace imlsgpu;
 

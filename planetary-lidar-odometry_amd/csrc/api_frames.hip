@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "context.h"
+#include "index.h"
 
 using namespace imlsgpu;
 
@@ -50,7 +51,7 @@ int batch_builds(imls_ctx* L, imls_ctx* const* ctxs, size_t n, bool fused, HostS
         timing |= ctxs[k]->timing == 1;
     }
     if (!any) return IMLS_OK;
-    // incremental FIFO targets (index.hip fifo_*): each member's own build on its stream (a merge of
+    // incremental FIFO targets (fifo_index.hip fifo_*): each member's own build on its stream (a merge of
     // sorted runs, not the batch's one radix sort), joined by the lead's stream
     for (size_t k = 0; k < n; ++k) {
         imls_ctx* c = ctxs[k];

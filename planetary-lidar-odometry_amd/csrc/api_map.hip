@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "context.h"
+#include "index.h"
 
 using namespace imlsgpu;
 
@@ -151,7 +152,7 @@ int imlsgpu::fifo_build(imls_ctx* c) {
     for (auto& e : c->fifo) {
         if (e.nk <= 0 || (live >> e.id & 1u)) continue;
         if (int rc = fifo_merge(s, K(c->mcur), V(c->mcur), c->m_n, fifo_run_keys(e.run.p, e.nk), (unsigned)e.id, e.nk,
-                                K(c->mcur ^ 1), V(c->mcur ^ 1), c->fscr, c->err))
+                                K(c->mcur ^ 1), V(c->mcur ^ 1), c->err))
             return rc;
         c->mcur ^= 1;
         c->m_n += e.nk;

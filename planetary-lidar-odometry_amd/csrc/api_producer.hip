@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "context.h"
+#include "index.h"
 
 using namespace imlsgpu;
 

@@ -53,7 +53,7 @@ struct imls_ctx {
     // map FIFO (accumulateTargetCloud, laser_odometry.cpp:116-136): the last max_queue_size filtered
     // scans, each SoA6 in its own slot, and their concatenation (oldest first) the index is built from
     // a FIFO entry: its raw SoA6 scan (the concatenation path), and for the incremental index its
-    // filtered points (fpt / fnr, NaN filter at the push) and its sorted run (index.hip)
+    // filtered points (fpt / fnr, NaN filter at the push) and its sorted run (fifo_index.hip)
     struct MapSlot {
         DevBuf buf, fpt, fnr, run;
         size_t n = 0;

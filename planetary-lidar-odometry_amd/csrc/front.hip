@@ -182,13 +182,6 @@ __global__ void k_front_init(int* ints, int n) {
     (void)n;
 }
 
-template <typename T>
-T* carve(char*& p, size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += ((n * sizeof(T) + 255) / 256) * 256;
-    return r;
-}
-
 }  // namespace
 
 int front_end_dev(hipStream_t s, const imls_front_params& p, const float* d_soa3, const float* h_soa3, size_t n_in,

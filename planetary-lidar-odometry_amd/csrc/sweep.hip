@@ -46,13 +46,6 @@ constexpr int kCtlBins = 4;            // ctl words before the bin sizes: droppe
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 unsigned blocks_of(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-template <typename T>
-T* carve(char*& p, size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += al256(n * sizeof(T));
-    return r;
-}
-
 // static_cast<int> as x86-64 evaluates it (cvttsd2si / cvttss2si): truncation, INT_MIN for NaN and
 // out-of-range values
 __device__ __forceinline__ int x86_d2i(double v) {

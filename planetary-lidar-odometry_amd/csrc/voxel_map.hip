@@ -23,12 +23,6 @@ namespace {
 constexpr unsigned long long kVoxSentinel = ~0ull;
 constexpr double kVoxLo = -1048576.0, kVoxHi = 1048575.0;   // −2²⁰ … 2²⁰ − 1
 
-template <typename T>
-T* carve(char*& p, size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += ((n * sizeof(T) + 255) / 256) * 256;
-    return r;
-}
 inline size_t part(size_t bytes) { return (bytes + 255) / 256 * 256; }
 inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 

@@ -2,7 +2,7 @@
 that each generator reaches the edge it is named for, and test_gpu_index_edges.py, which runs them on
 the device).  No GPU imports.
 
-The spatial index has three builders and one small-source path (csrc/index.hip): the full build
+The spatial index has three builders and one small-source path (csrc/index.hip, csrc/fifo_index.hip): the full build
 (morton_perm → k_gather → k_leaf_boxes → k_subtree), the batched build (build_batch, the k_*_b
 kernels), the incremental map-FIFO build (fifo_run_build, k_keep_*, k_merge_tile, k_fifo_gather, driven
 by fifo_build in csrc/api_map.hip) and k_small_order.  An index that drops, doubles or mis-boxes one
@@ -25,10 +25,10 @@ import numpy as np
 import imls_np
 
 BLOCK = 256                 # internal.h kBlock: boxes per k_subtree block per round
-MERGE_TILE = 2048           # index.hip kMergeTile: outputs per k_merge_tile block
+MERGE_TILE = 2048           # fifo_index.hip kMergeTile: outputs per k_merge_tile block
 MERGE_PER = MERGE_TILE // BLOCK
-KEEP_TILE = 4096            # index.hip kKeepTile: entries per k_keep_* block
-SMALL_ORDER_N = 2048        # internal.h kSmallOrderN
+KEEP_TILE = 4096            # fifo_index.hip kKeepTile: entries per k_keep_* block
+SMALL_ORDER_N = 2048        # index.h kSmallOrderN
 LEAVES = (4, 64)
 
 
@@ -345,7 +345,7 @@ def fifo_states(seq, queue):
     return out
 
 
-# ---- a numpy model of the tiled merge path (index.hip merge_split_at / k_merge_tile) -----------------
+# ---- a numpy model of the tiled merge path (fifo_index.hip merge_split_at / k_merge_tile) -----------------
 def model_keys(P, frame_of):
     """48-bit Morton keys of (n, 3) float32 points under the FIFO frame of `frame_of` (k_fifo_frame's
     cube: side 2 × the largest extent, origin half an extent below the bbox).  Equal points get equal

@@ -1,4 +1,4 @@
-"""The incremental index of the map FIFO (index.hip fifo_*, api_map.hip fifo_build): each scan pushed
+"""The incremental index of the map FIFO (fifo_index.hip fifo_*, api_map.hip fifo_build): each scan pushed
 into the FIFO (accumulateTargetCloud, /root/reference/src/laser_odometry.cpp:116-136) is NaN-filtered
 and Morton-sorted ONCE under a quantisation frame fixed for the FIFO; a registration compacts the
 previous merged order (the evicted scans' entries out) and merges the newest run into it, instead of

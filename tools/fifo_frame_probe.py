@@ -1,4 +1,4 @@
-"""Tree-quality probe of the FIFO index's quantisation frame (index.hip k_fifo_frame), on the CPU:
+"""Tree-quality probe of the FIFO index's quantisation frame (fifo_index.hip k_fifo_frame), on the CPU:
 config B's map (synth, the bench's pair 0) Morton-sorted under a candidate frame, 64-point leaves,
 the implicit binary tree over them; the cost proxy is the number of leaves / nodes whose box meets
 each sampled query's ball of its 20th-neighbour distance (what a kNN traversal must visit).  The
