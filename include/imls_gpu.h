@@ -51,9 +51,27 @@ typedef enum imls_solve_method {
     IMLS_SOLVE_LS = 0,          /* "LS"     → SolveMotionEstimationProblemLS (solver.cpp:74-166) */
     IMLS_SOLVE_RANSAC = 1,      /* "RANSAC" → SolveMotionEstimationProblemRANSAC (solver.cpp:222-385) */
     IMLS_SOLVE_WEIGHTED_LS = 2, /* "Weighted LS" (solver.cpp:168-220); unit weights when used directly */
-    IMLS_SOLVE_DRPM = 3         /* SolveMotionEstimationProblemDRPM (solver.cpp:499-603) on caller rows:
+    IMLS_SOLVE_DRPM = 3,        /* SolveMotionEstimationProblemDRPM (solver.cpp:499-603) on caller rows:
                                    imls_solve_correspondences only (RANSAC's final, not a loop method) */
+    IMLS_SOLVE_ROBUST = 4       /* robust M-estimator solve (below): a loop method and a stand-alone one */
 } imls_solve_method;
+
+/* The loss of IMLS_SOLVE_ROBUST.  With (a_i, b_i) the point-to-plane rows (solver.cpp:95-103), u_i the
+ * caller's weight (imls_solve_correspondences with weights, else 1) and x⁰ = 0, the solve runs
+ * K = robust_iterations re-weighted steps
+ *     r_i = a_i·xᵏ − b_i,   w_i = u_i·ψ(r_i; c),   H = Σ w_i a_i a_iᵀ,   g = Σ w_i a_i b_i,   xᵏ⁺¹ = H⁻¹ g
+ * over the valid rows (the column-pivoted 6×6 solve and rank rule of LS; unknowns past the rank are 0;
+ * with n < 6 rows of weight > 0 the rank is at most n, as for a QR of those rows)
+ * and turns x^K into Δ as LS does.  c = robust_scale.  At k = 0 the residual is −b_i, the residual
+ * under the pose the ICP loop has reached.  This is the cost ½ Σ ρ(r_i²) of the reference's Ceres
+ * problem (HuberLoss(0.1), solver.cpp:25-72) linearised at each ICP iteration's pose — not Ceres's
+ * own trust-region iterates.  Gates as LS: fewer valid rows than correspond_number inside the loop
+ * → IMLS_FRAME_TOO_FEW, no valid row → IMLS_FRAME_SOLVE_FAILED; the trace's n_kept = n_valid. */
+typedef enum imls_robust_loss {
+    IMLS_ROBUST_HUBER = 0,          /* ψ = 1 for |r| ≤ c, else c/|r| */
+    IMLS_ROBUST_CAUCHY = 1,         /* ψ = 1/(1 + r²/c²) */
+    IMLS_ROBUST_GEMAN_MCCLURE = 2   /* ψ = (c²/(c² + r²))² */
+} imls_robust_loss;
 
 /* solve_method.RANSAC.final_solve_method (config.json; solver.cpp:368-384) */
 typedef enum imls_final_method {
@@ -143,7 +161,20 @@ typedef struct imls_params {
     /* laser_odometry */
     int32_t transform_normal;         /* laser_odometry.transform_normal (laser_odometry.cpp:541-548) */
     int32_t max_queue_size;           /* laser_odometry.max_queue_size (map FIFO length) */
-    int32_t _reserved[4];
+    /* The struct's tail: the words reserved so far now hold the robust solve's parameters, so
+     * sizeof(imls_params) is what it was.  laser_odometry.solve_method.Robust — read only when
+     * solve_method is IMLS_SOLVE_ROBUST (a struct that zeroes its reserved words stays valid for
+     * every other method); then a loss outside the enum, robust_iterations outside 1 … 32 or a
+     * robust_scale that is not finite or ≤ 0 → IMLS_ERR_ARG.  (An anonymous struct in an anonymous
+     * union: C11; in C++ a GNU / MSVC extension, which -pedantic reports.) */
+    union {
+        int32_t _reserved[4];
+        struct {
+            int32_t robust_loss;          /* imls_robust_loss (Huber) */
+            int32_t robust_iterations;    /* K, re-weighted solves per ICP iteration (5) */
+            double robust_scale;          /* c (0.1: the reference's HuberLoss(0.1)) */
+        };
+    };
 } imls_params;
 
 /* Per-iteration record of imls_register_frame (the reference writes the same quantities to
@@ -237,7 +268,8 @@ int imls_set_defer(imls_ctx* ctx, int on);
  *   Weighted LS: every valid row, the caller's weights (else 1);
  *   RANSAC → LS: the same trim with ransac_ls_threshold over the inliers of the best hypothesis, w = 1;
  *   RANSAC → Weighted LS / DRPM: every inlier, w_i / Σw (solver.cpp:334-364);
- *   DRPM on caller rows: every row, the caller's weights.
+ *   DRPM on caller rows: every row, the caller's weights;
+ *   Robust: every valid row, w_i = u_i·ψ(a_i·x^{K−1} − b_i; c): the weights of its last 6×6 system.
  *
  * What it is: the formal covariance of that one linear solve — the linearisation at the pose BEFORE
  * the iteration's Δ, over the rows the solve used.  It mixes radians and metres, knows nothing of
@@ -426,7 +458,8 @@ int imls_solve(imls_ctx* ctx, double delta_out[16], int* ok);
 /* Replaces SolveMotionEstimationProblemLS / WeightedLS / RANSAC / DRPM (solver.cpp:74-385,
  * 499-603) on host arrays of N double triples (s = source, d = target, n = target normal; weights
  * nullable = unit; LS uses params.ls_threshold, RANSAC the ransac_* fields and the context's rand()
- * stream, DRPM drpm_threshold / drpm_stdev_points / drpm_stdev_normals). */
+ * stream, DRPM drpm_threshold / drpm_stdev_points / drpm_stdev_normals), or the robust solve
+ * (IMLS_SOLVE_ROBUST: the robust_* fields of the params in force, the weights as u_i). */
 int imls_solve_correspondences(imls_ctx* ctx, int32_t method, const double* s, const double* d,
                                const double* n, const double* weights, size_t N,
                                double delta_out[16], int* ok);

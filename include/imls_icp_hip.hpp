@@ -422,4 +422,19 @@ bool SolveMotionEstimationProblemDRPM(Vec3List& source_cloud, Vec3List& ref_clou
     return detail::solve(IMLS_SOLVE_DRPM, p, source_cloud, ref_cloud, ref_normals, w.data(), deltaTrans);
 }
 
+// The robust M-estimator solve (imls_gpu.h IMLS_SOLVE_ROBUST; no counterpart in solver.h — the cost of
+// the reference's Ceres problem, solver.cpp:25-72, linearised once): `iterations` re-weighted 6×6
+// solves under `loss` (imls_robust_loss) at scale c.  Bad loss / scale / iterations return false.
+template <class Vec3List, class Mat4>
+bool SolveMotionEstimationProblemRobust(Vec3List& source_cloud, Vec3List& ref_cloud, Vec3List& ref_normals,
+                                        Mat4& deltaTrans, const std::string& /*timestamp*/, const int loss,
+                                        const double scale, const int iterations) {
+    imls_params p = detail::thread_params();
+    p.solve_method = IMLS_SOLVE_ROBUST;
+    p.robust_loss = loss;
+    p.robust_scale = scale;
+    p.robust_iterations = iterations;
+    return detail::solve(IMLS_SOLVE_ROBUST, p, source_cloud, ref_cloud, ref_normals, nullptr, deltaTrans);
+}
+
 }  // namespace imls_hip

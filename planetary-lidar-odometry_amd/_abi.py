@@ -15,7 +15,8 @@ LIB_PATH = PKG_DIR / "csrc" / "libimls_gpu.so"
 
 IMLS_OK, IMLS_ERR_ARG, IMLS_ERR_DEVICE, IMLS_ERR_STATE, IMLS_ERR_UNSUPPORTED, IMLS_ERR_CAPACITY = 0, -1, -2, -3, -4, -5
 IMLS_MATCH_IMLS, IMLS_MATCH_PLANE_ICP = 0, 1
-IMLS_SOLVE_LS, IMLS_SOLVE_RANSAC, IMLS_SOLVE_WEIGHTED_LS, IMLS_SOLVE_DRPM = 0, 1, 2, 3
+IMLS_SOLVE_LS, IMLS_SOLVE_RANSAC, IMLS_SOLVE_WEIGHTED_LS, IMLS_SOLVE_DRPM, IMLS_SOLVE_ROBUST = 0, 1, 2, 3, 4
+IMLS_ROBUST_HUBER, IMLS_ROBUST_CAUCHY, IMLS_ROBUST_GEMAN_MCCLURE = 0, 1, 2   # imls_robust_loss
 IMLS_FINAL_LS, IMLS_FINAL_WEIGHTED_LS, IMLS_FINAL_DRPM = 0, 1, 2
 IMLS_FRAME_MAX_ITERS, IMLS_FRAME_CONVERGED, IMLS_FRAME_TOO_FEW, IMLS_FRAME_SOLVE_FAILED = 0, 1, 2, 3
 REJECT_NAMES = ("no_normal", "too_far", "invalid_normal", "normal_constraint", "mls_fail", "nan_inf_height")
@@ -37,8 +38,20 @@ STATUS_NAMES = {0: "IMLS_OK", -1: "IMLS_ERR_ARG", -2: "IMLS_ERR_DEVICE", -3: "IM
 _i32, _u32, _f64, _f32 = C.c_int32, C.c_uint32, C.c_double, C.c_float
 
 
+class _ImlsRobust(C.Structure):
+    _fields_ = [("robust_loss", _i32), ("robust_iterations", _i32), ("robust_scale", _f64)]
+
+
+class _ImlsParamsTail(C.Union):
+    """The tail union of `imls_params`: the reserved words, which hold the robust solve's fields."""
+    _anonymous_ = ("robust",)
+    _fields_ = [("words", _i32 * 4), ("robust", _ImlsRobust)]
+
+
 class ImlsParams(C.Structure):
-    """Field-for-field mirror of `imls_params` (include/imls_gpu.h)."""
+    """Field-for-field mirror of `imls_params` (include/imls_gpu.h); robust_loss, robust_iterations
+    and robust_scale are attributes through the anonymous tail union."""
+    _anonymous_ = ("_reserved",)
     _fields_ = [
         ("matching_method", _i32), ("correspond_number", _i32),
         ("h", _f64), ("r", _f64),
@@ -59,7 +72,7 @@ class ImlsParams(C.Structure):
         ("drpm_threshold", _f64), ("drpm_stdev_points", _f64), ("drpm_stdev_normals", _f64),
         ("ransac_seed", _u32),
         ("transform_normal", _i32), ("max_queue_size", _i32),
-        ("_reserved", _i32 * 4),
+        ("_reserved", _ImlsParamsTail),
     ]
 
     def as_dict(self) -> dict:
@@ -128,6 +141,7 @@ def default_params() -> ImlsParams:
     p.drpm_threshold, p.drpm_stdev_points, p.drpm_stdev_normals = 0.05, 0.02, 0.05
     p.ransac_seed = 1
     p.transform_normal, p.max_queue_size = 0, 1
+    p.robust_loss, p.robust_iterations, p.robust_scale = IMLS_ROBUST_HUBER, 5, 0.1
     return p
 
 

@@ -4,7 +4,7 @@ Accepts the reference's config.json layout unchanged (the ``laser_odometry`` sec
 laser_odometry.cpp reads at 487-518, 570, 606, 640-641 and the dispatcher 183-243) plus one new
 key, ``laser_odometry.backend`` ("hip" — the only backend this package ships).  Method names are
 the reference's strings: matching "IMLS" / "plane_ICP"; solving "LS" / "RANSAC" / "Ceres" / "ICP" /
-"Teaser"; RANSAC final "LS" / "Weighted LS" / "DRPM".
+"Teaser", plus this package's "Robust" (the M-estimator solve, block ``solve_method.Robust``); RANSAC final "LS" / "Weighted LS" / "DRPM".
 
 producer_from_config() reads the ``scan_registration`` section (scan_registration.cpp:771-799, 935,
 1073, 1132-1145, 1451, 1464, 1479) the same way: compute_normal_method "pca" on format
@@ -25,7 +25,11 @@ MATCHING = {"IMLS": _abi.IMLS_MATCH_IMLS, "plane_ICP": _abi.IMLS_MATCH_PLANE_ICP
 # "Weighted LS" is only a RANSAC final method there: as a top-level name it hits "Invalid
 # SOLVE_METHOD!", so it is rejected here too (the C ABI's IMLS_SOLVE_WEIGHTED_LS is an extension
 # for callers that want a unit-weight WLS loop, never produced from a config file).
-SOLVING = {"LS": _abi.IMLS_SOLVE_LS, "RANSAC": _abi.IMLS_SOLVE_RANSAC}
+SOLVING = {"LS": _abi.IMLS_SOLVE_LS, "RANSAC": _abi.IMLS_SOLVE_RANSAC, "Robust": _abi.IMLS_SOLVE_ROBUST}
+# solve_method.Robust.loss (the robust M-estimator solve, include/imls_gpu.h imls_robust_loss)
+ROBUST_LOSS = {"huber": _abi.IMLS_ROBUST_HUBER, "cauchy": _abi.IMLS_ROBUST_CAUCHY,
+               "geman_mcclure": _abi.IMLS_ROBUST_GEMAN_MCCLURE}
+ROBUST_MAX_ITERATIONS = 32
 FINAL = {"LS": _abi.IMLS_FINAL_LS, "Weighted LS": _abi.IMLS_FINAL_WEIGHTED_LS, "DRPM": _abi.IMLS_FINAL_DRPM}
 # Third-party solver engines (solver.cpp:25-72, 387-483): outside the GPU path.
 UNSUPPORTED_SOLVERS = ("Ceres", "ICP", "Teaser")
@@ -44,8 +48,11 @@ def load(path: str | pathlib.Path | None = None) -> dict:
         return json.load(f)
 
 
-def params_from_config(cfg: dict) -> _abi.ImlsParams:
+def params_from_config(cfg: dict, ceres: str | None = None) -> _abi.ImlsParams:
     """Build imls_params from the reference key paths.  Unknown method names raise ConfigError.
+    ``ceres="robust"`` (opt-in; by default "Ceres" is refused) maps solve_method "Ceres" to the Robust
+    solve with the reference's HuberLoss(0.1) and K = min(Ceres.max_iterations, 32): the same cost,
+    linearised at each ICP iteration's pose — not Ceres's own iterates.
     Deliberate change, documented in INTEGRATION.md: the reference prints "Invalid
     MATCHING_METHOD!" / "Invalid SOLVE_METHOD!" and keeps running with every frame's solve failing
     (rPose = I for every frame); this fails once, at configuration time."""
@@ -77,6 +84,13 @@ def params_from_config(cfg: dict) -> _abi.ImlsParams:
         p.picp_normal_angle_constraint = int(bool(pi["normal_angle_constraint"]["enabled"]))
         p.picp_angle_diff_threshold = float(pi["normal_angle_constraint"]["angle_diff_threshold"])
     method = sm["method"]
+    if ceres not in (None, "robust"):
+        raise ConfigError(f"ceres={ceres!r}: only 'robust' (or None: refuse the name) is known")
+    rb = sm.get("Robust", {})
+    if method == "Ceres" and ceres == "robust":
+        method = "Robust"
+        rb = {"loss": "huber", "scale": 0.1,
+              "iterations": min(int(sm.get("Ceres", {}).get("max_iterations", 20)), ROBUST_MAX_ITERATIONS)}
     if method in UNSUPPORTED_SOLVERS:
         raise ConfigError(f"solve_method {method!r} is a third-party solver engine outside the GPU path")
     if method not in SOLVING:
@@ -86,6 +100,19 @@ def params_from_config(cfg: dict) -> _abi.ImlsParams:
     p.delta_dist_threshold = float(sm["delta_dist_threshold"])
     p.delta_angle_threshold = float(sm["delta_angle_threshold"])
     p.ls_threshold = float(sm["LS"]["threshold"])
+    if "loss" in rb:
+        if rb["loss"] not in ROBUST_LOSS:
+            raise ConfigError(f"Invalid Robust.loss {rb['loss']!r}: one of {sorted(ROBUST_LOSS)}")
+        p.robust_loss = ROBUST_LOSS[rb["loss"]]
+    if "scale" in rb:
+        p.robust_scale = float(rb["scale"])
+    if "iterations" in rb:
+        p.robust_iterations = int(rb["iterations"])
+    if method == "Robust":
+        if not 1 <= p.robust_iterations <= ROBUST_MAX_ITERATIONS:
+            raise ConfigError(f"Robust.iterations {p.robust_iterations}: the GPU path takes 1 … {ROBUST_MAX_ITERATIONS}")
+        if not (0.0 < p.robust_scale < float("inf")):
+            raise ConfigError(f"Robust.scale {p.robust_scale!r} must be finite and > 0")
     rs = sm["RANSAC"]
     p.ransac_max_iterations = int(rs["max_iterations"])
     p.ransac_distance_threshold = float(rs["distance_threshold"])

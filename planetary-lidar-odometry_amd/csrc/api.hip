@@ -105,6 +105,9 @@ KParams make_kparams(const imls_params& p, const Options& o) {
     k.tv_sigma = p.tensor_sigma;
     k.tv_thr = p.tensor_distance_threshold;
     k.tv_skin = (float)o.tv_skin;
+    k.robust_loss = p.robust_loss;
+    k.robust_iters = p.robust_iterations;
+    k.robust_scale = p.robust_scale;
     // angle_reject reads "cosine above cos_thr" as "angle below the threshold", which holds for
     // thresholds in [0°, 180°] only.  The reference compares the angle itself (acos(ca)·180/π > thr,
     // any double): outside that range the cosine of the nearer end stands in, and the exact branch
@@ -129,8 +132,15 @@ int check_params(imls_ctx* c, const imls_params* p) {
     }
     if (!p->get_normals && p->recompute_normal_count_mode && (p->search_number_normal < 1 || p->search_number_normal > 32))
         return fail(c, IMLS_ERR_ARG, "search_number_normal must be in [1, 32]");
-    if (p->solve_method != IMLS_SOLVE_LS && p->solve_method != IMLS_SOLVE_WEIGHTED_LS && p->solve_method != IMLS_SOLVE_RANSAC)
-        return fail(c, IMLS_ERR_UNSUPPORTED, "solve_method must be LS, Weighted LS or RANSAC (Ceres/ICP/Teaser stay on the CPU path)");
+    if (p->solve_method != IMLS_SOLVE_LS && p->solve_method != IMLS_SOLVE_WEIGHTED_LS && p->solve_method != IMLS_SOLVE_RANSAC &&
+        p->solve_method != IMLS_SOLVE_ROBUST)
+        return fail(c, IMLS_ERR_UNSUPPORTED, "solve_method must be LS, Weighted LS, RANSAC or Robust (Ceres/ICP/Teaser stay on the CPU path)");
+    if (p->solve_method == IMLS_SOLVE_ROBUST) {   // (the robust fields are read for this method only)
+        if (p->robust_loss != IMLS_ROBUST_HUBER && p->robust_loss != IMLS_ROBUST_CAUCHY && p->robust_loss != IMLS_ROBUST_GEMAN_MCCLURE)
+            return fail(c, IMLS_ERR_ARG, "robust_loss must be Huber, Cauchy or Geman-McClure");
+        if (p->robust_iterations < 1 || p->robust_iterations > 32) return fail(c, IMLS_ERR_ARG, "robust_iterations must be in [1, 32]");
+        if (!std::isfinite(p->robust_scale) || !(p->robust_scale > 0)) return fail(c, IMLS_ERR_ARG, "robust_scale must be finite and > 0");
+    }
     if (p->solve_method == IMLS_SOLVE_RANSAC) {
         if (p->ransac_final_method != IMLS_FINAL_LS && p->ransac_final_method != IMLS_FINAL_WEIGHTED_LS &&
             p->ransac_final_method != IMLS_FINAL_DRPM)
@@ -282,6 +292,12 @@ ProjectLaunch project_launch(imls_ctx* c, const TreeView& t, const KParams& kp, 
     return L;
 }
 
+// the solve sequence of L.kp.solve_method: the robust chain (solve_robust.hip), or launch_solve's
+static void enqueue_solve(hipStream_t s, const SolveLaunch& L) {
+    if (L.kp.solve_method == IMLS_SOLVE_ROBUST) launch_solve_robust(s, L);
+    else launch_solve(s, L);
+}
+
 SolveLaunch solve_launch(imls_ctx* c, imls_iter_trace* tr, int update_pose) {
     SolveLaunch L{};
     L.N = c->N;
@@ -333,6 +349,8 @@ int info_enqueue(imls_ctx* c, imls_ctx* timer, hipStream_t s, int method, const 
     L.iters = c->st.iters;
     L.in_loop = in_loop;
     L.solve_method = method;
+    L.robust_loss = c->kp.robust_loss;
+    L.robust_scale = c->kp.robust_scale;
     L.slabs = (double*)(base + kInfoSlabOff);
     L.out = (struct imls_pose_info*)(base + kInfoOutOff);
     if (method == IMLS_SOLVE_RANSAC) {
@@ -653,6 +671,9 @@ void imls_default_params(imls_params* p) {
     p->ransac_seed = 1;
     p->transform_normal = 0;
     p->max_queue_size = 1;
+    p->robust_loss = IMLS_ROBUST_HUBER;
+    p->robust_iterations = 5;
+    p->robust_scale = 0.1;
 }
 
 imls_ctx* imls_create(int device, const imls_params* p) {
@@ -1018,7 +1039,7 @@ int imls_solve(imls_ctx* c, double delta_out[16], int* ok) {
     if (int rc = info_begin(c, c->N, c->stream)) return rc;
     int slot;
     timed_begin(c, kTimeSolve, slot);
-    launch_solve(c->stream, solve_launch(c, nullptr, 0));
+    enqueue_solve(c->stream, solve_launch(c, nullptr, 0));
     timed_end(c, kTimeSolve, slot);
     if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 0)) return rc;
     int status = 0;
@@ -1036,9 +1057,15 @@ int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, con
     if (!c || !s || !d || !n || !delta_out) return IMLS_ERR_ARG;
     c->info_state = 0;
     if (method != IMLS_SOLVE_LS && method != IMLS_SOLVE_WEIGHTED_LS && method != IMLS_SOLVE_RANSAC &&
-        method != IMLS_SOLVE_DRPM)
+        method != IMLS_SOLVE_DRPM && method != IMLS_SOLVE_ROBUST)
         return fail(c, IMLS_ERR_UNSUPPORTED, "method");
     if (N > (size_t)0x3fffffff) return fail(c, IMLS_ERR_ARG, "N too large");
+    if (method == IMLS_SOLVE_ROBUST && c->P.solve_method != IMLS_SOLVE_ROBUST) {
+        // the robust fields of the params in force were not checked under another method
+        imls_params q = c->P;
+        q.solve_method = IMLS_SOLVE_ROBUST;
+        if (int rc = check_params(c, &q)) return rc;
+    }
     if (int rc = check_device(c)) return rc;
     if (int rc = ensure_solve(c, (int)std::max<size_t>(N, 1))) return rc;
     size_t bytes = (9 * N + N) * 8 + 64;
@@ -1070,7 +1097,7 @@ int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, con
     L.rows_d = r;
     L.weights = dw;
     L.rows_are_double = 1;
-    launch_solve(c->stream, L);
+    enqueue_solve(c->stream, L);
     if (int rc = info_enqueue(c, c, c->stream, method, r, dw, (int)N, 0)) return rc;
     int status = 0;
     hipMemcpyAsync(delta_out, c->st.delta, 16 * 8, hipMemcpyDeviceToHost, c->stream);
@@ -1130,7 +1157,7 @@ int imls_register_frame_async(imls_ctx* c) {
             }
         }
         timed_begin(c, kTimeSolve, slot);
-        launch_solve(c->stream, solve_launch(c, tr + it, 1));
+        enqueue_solve(c->stream, solve_launch(c, tr + it, 1));
         timed_end(c, kTimeSolve, slot);
     }
     if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 1)) return rc;

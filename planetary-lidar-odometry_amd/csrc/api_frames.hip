@@ -221,14 +221,14 @@ __global__ void k_batch_results(const PairDev* __restrict__ tab, int n, double* 
     }
 }
 
-// The batched path covers both matchers (tensor-voting normals included) with the LS-family solvers
-// and RANSAC (+ its LS / weighted LS / DRPM final solve); the projected-distance rule and the exact
+// The batched path covers both matchers (tensor-voting normals included) with the LS-family solvers,
+// the robust solve and RANSAC (+ its LS / weighted LS / DRPM final solve); the projected-distance rule and the exact
 // per-lane mode keep one launch sequence per frame (each on its own context stream, so they still
 // overlap).
 bool batch_fusable(const imls_ctx* c) {
     return !c->lane_mode && !c->kp.proj &&
            (c->P.solve_method == IMLS_SOLVE_LS || c->P.solve_method == IMLS_SOLVE_WEIGHTED_LS ||
-            c->P.solve_method == IMLS_SOLVE_RANSAC);
+            c->P.solve_method == IMLS_SOLVE_RANSAC || c->P.solve_method == IMLS_SOLVE_ROBUST);
 }
 
 PairDev pair_dev(imls_ctx* c) {
@@ -397,7 +397,9 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         if (kp.solve_method == IMLS_SOLVE_RANSAC) {
             if (launch_ransac_batch(s, tab, nh, (int)n, kp, rp, it))
                 return fail(L, IMLS_ERR_CAPACITY, "RANSAC batch larger than kMaxRansacBatch frames");
-        } else
+        } else if (kp.solve_method == IMLS_SOLVE_ROBUST)
+            launch_solve_robust_batch(s, tab, nh, (int)n, kp, it);
+        else
             launch_solve_batch(s, tab, nh, (int)n, kp, it);
         timed_end(L, kTimeSolve, slot);
     }

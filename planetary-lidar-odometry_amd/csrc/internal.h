@@ -88,6 +88,9 @@ struct KParams {
     int tv_k;                 // use_tensor_voting.k (≤ kTvMaxK)
     double tv_sigma, tv_thr;  // use_tensor_voting.sigma, .distance_threshold
     float tv_skin;            // TV ball lists reused while the query moved ≤ skin (m); 0 = every iteration walks the tree
+    int robust_loss;          // imls_robust_loss (solve_method IMLS_SOLVE_ROBUST only, as the next two)
+    int robust_iters;         // K: re-weighted 6×6 solves per robust solve (1 … 32)
+    double robust_scale;      // c of ψ(r; c)
 };
 // the parameters of ICP iteration `it`'s projection launch (packet size of the traversal)
 inline KParams kp_at(const KParams& k, int it) {
@@ -198,7 +201,8 @@ struct InfoExport {
     int degenerate;           // DRPM took the SNR-weighted branch
     int pad;
 };
-enum InfoKind { kInfoNone = 0, kInfoAll = 1, kInfoTrim = 2, kInfoDrpm = 3 };
+// (kInfoRobust: every valid row, weight u·ψ(a·x0 − b): x0 = x^{K−1}, the vector the last weights were taken under)
+enum InfoKind { kInfoNone = 0, kInfoAll = 1, kInfoTrim = 2, kInfoDrpm = 3, kInfoRobust = 4 };
 
 // Solver scratch living in device memory (one per context).
 struct SolveState {
@@ -455,6 +459,14 @@ void launch_solve_batch(hipStream_t s, const PairDev* tab, const int* n_host, in
 // pass 1 over every frame's RANSAC inlier rows (weighted: w / Σw)
 void launch_rows_pass1_batch(hipStream_t s, const PairDev* tab, const int* cap_host, int npairs, int weighted);
 
+// solve_robust.hip — the robust M-estimator solve (IMLS_SOLVE_ROBUST): K re-weighted 6×6 solves of
+// the point-to-plane rows under ψ ∈ {Huber, Cauchy, Geman-McClure}, then Δ and the pose update.
+// Float rows of ≤ kSmallRows: one block; larger frames and fp64 rows: K × (grid pass, one-block solve).
+struct SolveLaunch;
+void launch_solve_robust(hipStream_t s, const SolveLaunch& L);
+// every frame of tab (float rows of the batched projection), one launch per step for the whole batch
+void launch_solve_robust_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp, int it);
+
 // pose_info.hip — the covariance / degeneracy report of the last solve (imls_capture_pose_info)
 struct InfoLaunch {
     const float4 *cs, *cd, *cn;        // float rows of the projection, or
@@ -467,6 +479,8 @@ struct InfoLaunch {
     const int *status, *iters;         // the frame's (SolveState)
     int in_loop;                       // a registration (its iteration must be the frame's last)
     int solve_method, final_method;
+    int robust_loss;                   // ψ of a robust solve's weights (kInfoRobust)
+    double robust_scale;
     double* slabs;                     // [info_blocks(N) × kInfoTerms]
     struct imls_pose_info* out;               // device
 };

@@ -5,7 +5,9 @@
 //                 the host API / the RANSAC inliers share the code).  Membership in the solve's final
 //                 system comes from the solve's own export (internal.h InfoExport): every valid row, or —
 //                 a trimmed LS — the rows of the closed interval [(key_lo, row_lo), (key_hi, row_hi)]
-//                 of the total order (|r₁| bits, row).  The key is recomputed with the expression the
+//                 of the total order (|r₁| bits, row); or — a robust solve — every valid row with the
+//                 weights of its last 6×6 system, u·ψ(a·x0 − b) under the exported x0 = x^{K−1}
+//                 (robust_psi and the residual expression of solve_robust.hip).  The key is recomputed with the expression the
 //                 solver uses (resid_hist_core / solve_small_body; -ffp-contract=off: the same bits).
 //                 Per kept row, in fp64: 21 terms of w·a·aᵀ, 6 of w·a·b, w·b², w, 1 and w·(a·x − b)²
 //                 (x is exported before the pass starts, so the residual needs no launch of its own).
@@ -45,7 +47,7 @@ __device__ __forceinline__ void info_block_sum(double (&v)[kInfoTerms], double* 
 }
 
 __global__ __launch_bounds__(kBlock) void k_info_rows(Rows rows, int N, const InfoExport* __restrict__ ex,
-                                                       double* __restrict__ slabs) {
+                                                       double* __restrict__ slabs, int robust_loss, double robust_scale) {
     __shared__ double red[(kBlock / 64) * kInfoTerms];
     const int kind = ex->kind;
     if (kind == kInfoNone) return;        // no solve succeeded: k_info_final reports zeros
@@ -62,6 +64,11 @@ __global__ __launch_bounds__(kBlock) void k_info_rows(Rows rows, int N, const In
             for (int k = 1; k < 6; ++k) r1 = r1 + a[k] * ex->x0[k];
             const unsigned long long kb = (unsigned long long)__double_as_longlong(fabs(r1 - b));
             in = info_pair_le(ex->key_lo, ex->row_lo, kb, (unsigned)i) && info_pair_le(kb, (unsigned)i, ex->key_hi, ex->row_hi);
+        }
+        if (kind == kInfoRobust) {
+            double r0 = a[0] * ex->x0[0];
+            for (int k = 1; k < 6; ++k) r0 = r0 + a[k] * ex->x0[k];
+            wt = wt * robust_psi(robust_loss, robust_scale, r0 - b);
         }
         if (in) {
             double wa[6];
@@ -211,7 +218,7 @@ void launch_pose_info(hipStream_t s, const InfoLaunch& L) {
         rows.dn = L.rows_d + 6 * c;
     }
     const int nb = info_blocks(L.N);
-    k_info_rows<<<nb, kBlock, 0, s>>>(rows, L.N, L.ex, L.slabs);
+    k_info_rows<<<nb, kBlock, 0, s>>>(rows, L.N, L.ex, L.slabs, L.robust_loss, L.robust_scale);
     k_info_final<<<1, 256, 0, s>>>(InfoFinalArgs{L.ex, L.status, L.iters, L.in_loop, L.solve_method, L.final_method,
                                                   L.slabs, nb, L.out});
 }

@@ -43,6 +43,20 @@ struct Rows {
     }
 };
 
+// ψ(r; c) of the robust solve (IMLS_SOLVE_ROBUST), the factor a row's weight takes from its residual:
+// Huber 1 for |r| ≤ c, else c/|r|; Cauchy 1/(1 + r²/c²); Geman-McClure (c²/(c² + r²))².  Shared by
+// the solver (solve_robust.hip) and the pose-info pass, which recomputes the last weights.
+__device__ __forceinline__ double robust_psi(int loss, double c, double r) {
+    if (loss == IMLS_ROBUST_HUBER) {
+        const double ar = fabs(r);
+        return ar <= c ? 1.0 : c / ar;
+    }
+    const double c2 = c * c, r2 = r * r;
+    if (loss == IMLS_ROBUST_CAUCHY) return 1.0 / (1.0 + r2 / c2);
+    const double t = c2 / (c2 + r2);
+    return t * t;
+}
+
 // Rows of a batched frame: the projection's float rows (src 0) or the frame's RANSAC inlier rows
 // (src 1: fp64, device-side count; weights w / Σw when weighted) — what launch_solve builds for the
 // same solve of a one-frame launch.
@@ -210,7 +224,10 @@ __device__ inline int solve6(const double* ne, double x[6]) {
 // every candidate row, and not the one-wave form's chain of LDS permutes per pivot (element (r, c) in
 // lane 6r + c: 3.6 µs per solve vs 2.8 here, tools/frame_probe.py phases).  Every lane (or the one
 // calling lane) holds the whole system and performs exactly solve6's operations: x is solve6's bit for bit.
-__device__ __forceinline__ int solve6_u(const double* ne, double x[6]) {
+// max_rank (wave-uniform; the robust solve passes its row count): pivots stop there.  A sum of n < 6
+// dyads has rank ≤ n, which QR on the n rows gets for free; the Schur complement's rounding residue
+// (relative ε, so √ε as a pivot) would pass the rank test.  The default 6 folds the test away.
+__device__ __forceinline__ int solve6_u(const double* ne, double x[6], int max_rank = 6) {
     double A[6][6], g[6];
     int perm[6];
     {
@@ -233,6 +250,10 @@ __device__ __forceinline__ int solve6_u(const double* ne, double x[6]) {
         for (int q = j + 1; q < 6; ++q)
             if (A[q][q] > best) { best = A[q][q]; p = q; }
         p = __builtin_amdgcn_readfirstlane(p);
+        if (j >= max_rank) {
+            rank = j;
+            break;
+        }
 #pragma unroll
         for (int q = j + 1; q < 6; ++q) {
             if (q == p) {                 // uniform: one taken branch per pivot

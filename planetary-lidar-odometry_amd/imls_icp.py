@@ -906,6 +906,26 @@ def SolveMotionEstimationProblemDRPM(source_cloud, ref_cloud, ref_normals, weigh
                                      _triples(ref_normals), np.asarray(weights, dtype=np.float64))
 
 
+def SolveMotionEstimationProblemRobust(source_cloud, ref_cloud, ref_normals, timestamp: str = "", loss: str = "huber",
+                                       scale: float = 0.1, iterations: int = 5):
+    """The robust M-estimator solve (IMLS_SOLVE_ROBUST, include/imls_gpu.h): `iterations` re-weighted
+    6×6 solves under `loss` ("huber" / "cauchy" / "geman_mcclure") at scale c → (flag, deltaTrans 4×4).
+    The defaults are the reference's Ceres cost, HuberLoss(0.1) (solver.cpp:25-72), linearised once."""
+    if loss not in _config.ROBUST_LOSS:
+        raise _config.ConfigError(f"Invalid Robust.loss {loss!r}: one of {sorted(_config.ROBUST_LOSS)}")
+    ctx = _solver_ctx()
+    saved = _abi.ImlsParams.from_buffer_copy(ctx.params)
+    p = _abi.ImlsParams.from_buffer_copy(saved)
+    p.solve_method = _abi.IMLS_SOLVE_ROBUST      # the robust fields are checked under this method
+    p.robust_loss, p.robust_scale, p.robust_iterations = _config.ROBUST_LOSS[loss], float(scale), int(iterations)
+    ctx.set_params(p)
+    try:
+        return ctx.solve_correspondences(_abi.IMLS_SOLVE_ROBUST, _triples(source_cloud), _triples(ref_cloud),
+                                         _triples(ref_normals))
+    finally:
+        ctx.set_params(saved)
+
+
 def solveMotionEstimationProblem(solve_method: str, in_cloud_vec, ref_cloud_vec, ref_normal, timestamp: str = "",
                                  cfg: Optional[dict] = None):
     """laser_odometry.cpp:173-275: string dispatch with parameters read from the config each call."""
@@ -920,6 +940,11 @@ def solveMotionEstimationProblem(solve_method: str, in_cloud_vec, ref_cloud_vec,
             float(rs["distance_threshold"]), float(rs["min_inliers_percentage"]), float(rs["huber_threshold"]),
             str(rs["final_solve_method"]), float(rs["LS_threshold"]), float(rs["DRPM_threshold"]),
             float(rs["DRPM_stdev_points"]), float(rs["DRPM_stdev_normals"]))
+    if solve_method == "Robust":
+        rb = sm.get("Robust", {})
+        return SolveMotionEstimationProblemRobust(in_cloud_vec, ref_cloud_vec, ref_normal, timestamp,
+                                                  str(rb.get("loss", "huber")), float(rb.get("scale", 0.1)),
+                                                  int(rb.get("iterations", 5)))
     if solve_method in _config.UNSUPPORTED_SOLVERS:
         raise _abi.ImlsError(_abi.IMLS_ERR_UNSUPPORTED, f"solve_method {solve_method!r} is not on the GPU path")
     # the reference prints "Invalid SOLVE_METHOD!" and returns false (laser_odometry.cpp:269-272)

@@ -54,7 +54,7 @@ def run_halo_block(odo, frames, halo, block):
               or getattr(getattr(odo, "ctx", None), "params", None))
     if params is not None and int(getattr(params, "solve_method", 0)) == _abi.IMLS_SOLVE_RANSAC:
         raise ValueError("run_halo_block: RANSAC draws one rand() stream across the sequence; a halo "
-                         "split is exact only for LS / Weighted LS — split whole sequences instead")
+                         "split is exact only for LS / Weighted LS / Robust — split whole sequences instead")
     for k in halo:
         odo.map_push(frames[k][0])
     rel = []
