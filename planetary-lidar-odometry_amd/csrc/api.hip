@@ -15,6 +15,7 @@
 
 #include "context.h"
 #include "index.h"
+#include "solve.h"
 
 using namespace imlsgpu;
 
@@ -292,12 +293,6 @@ ProjectLaunch project_launch(imls_ctx* c, const TreeView& t, const KParams& kp, 
     return L;
 }
 
-// the solve sequence of L.kp.solve_method: the robust chain (solve_robust.hip), or launch_solve's
-static void enqueue_solve(hipStream_t s, const SolveLaunch& L) {
-    if (L.kp.solve_method == IMLS_SOLVE_ROBUST) launch_solve_robust(s, L);
-    else launch_solve(s, L);
-}
-
 SolveLaunch solve_launch(imls_ctx* c, imls_iter_trace* tr, int update_pose) {
     SolveLaunch L{};
     L.N = c->N;
@@ -337,7 +332,7 @@ int info_begin(imls_ctx* c, int rows, hipStream_t s) {
 // The pass itself, behind the solve sequence on stream s (timed as kind 13 on `timer`, the context
 // whose stream s is), and the report's copy into pinned memory.  method: the solve method of the
 // sequence; rows_d / weights: the fp64 rows of a host-API solve (null: the projection's float rows);
-// N: their count.  RANSAC reads its inlier rows where launch_solve left them.
+// N: their count.  RANSAC reads its inlier rows where launch_ransac left them.
 int info_enqueue(imls_ctx* c, imls_ctx* timer, hipStream_t s, int method, const double* rows_d, const double* weights, int N,
                  int in_loop) {
     if (!c->st.info) return IMLS_OK;
@@ -1039,7 +1034,7 @@ int imls_solve(imls_ctx* c, double delta_out[16], int* ok) {
     if (int rc = info_begin(c, c->N, c->stream)) return rc;
     int slot;
     timed_begin(c, kTimeSolve, slot);
-    enqueue_solve(c->stream, solve_launch(c, nullptr, 0));
+    launch_solve(c->stream, solve_launch(c, nullptr, 0));
     timed_end(c, kTimeSolve, slot);
     if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 0)) return rc;
     int status = 0;
@@ -1097,7 +1092,7 @@ int imls_solve_correspondences(imls_ctx* c, int32_t method, const double* s, con
     L.rows_d = r;
     L.weights = dw;
     L.rows_are_double = 1;
-    enqueue_solve(c->stream, L);
+    launch_solve(c->stream, L);
     if (int rc = info_enqueue(c, c, c->stream, method, r, dw, (int)N, 0)) return rc;
     int status = 0;
     hipMemcpyAsync(delta_out, c->st.delta, 16 * 8, hipMemcpyDeviceToHost, c->stream);
@@ -1157,7 +1152,7 @@ int imls_register_frame_async(imls_ctx* c) {
             }
         }
         timed_begin(c, kTimeSolve, slot);
-        enqueue_solve(c->stream, solve_launch(c, tr + it, 1));
+        launch_solve(c->stream, solve_launch(c, tr + it, 1));
         timed_end(c, kTimeSolve, slot);
     }
     if (int rc = info_enqueue(c, c, c->stream, c->P.solve_method, nullptr, nullptr, c->N, 1)) return rc;

@@ -10,6 +10,7 @@
 
 #include "context.h"
 #include "index.h"
+#include "solve.h"
 
 using namespace imlsgpu;
 
@@ -394,13 +395,8 @@ int frames_async(imls_ctx* const* ctxs, size_t n) {
         launch_project_batch(s, tab, nh, (int)n, kp, it, it > 0 && L->temporal_seed);
         timed_end(L, kTimeProject, slot);
         timed_begin(L, kTimeSolve, slot);
-        if (kp.solve_method == IMLS_SOLVE_RANSAC) {
-            if (launch_ransac_batch(s, tab, nh, (int)n, kp, rp, it))
-                return fail(L, IMLS_ERR_CAPACITY, "RANSAC batch larger than kMaxRansacBatch frames");
-        } else if (kp.solve_method == IMLS_SOLVE_ROBUST)
-            launch_solve_robust_batch(s, tab, nh, (int)n, kp, it);
-        else
-            launch_solve_batch(s, tab, nh, (int)n, kp, it);
+        if (launch_solve_frames(s, tab, nh, (int)n, kp, rp, it))
+            return fail(L, IMLS_ERR_CAPACITY, "RANSAC batch larger than kMaxRansacBatch frames");
         timed_end(L, kTimeSolve, slot);
     }
     // every capturing member's pose-info pass, the lone frame's two launches on the same rows: the

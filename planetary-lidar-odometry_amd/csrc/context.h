@@ -216,6 +216,7 @@ struct imls_ctx {
 // Helpers that more than one api*.hip unit calls (each commented at its definition).  Hidden: they are
 // internal to the library and stay out of its dynamic symbol table.
 namespace imlsgpu {
+struct RansacParams;   // solve.h
 #pragma GCC visibility push(hidden)
 // api.hip
 int fail(imls_ctx* c, int code, const std::string& m);

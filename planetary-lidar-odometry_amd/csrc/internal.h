@@ -228,7 +228,7 @@ struct SolveState {
     InfoExport* info;         // null unless pose-info capture is on (then every solve exports)
 };
 
-// RANSAC state of one context (ransac.hip), carved from its RANSAC scratch by ransac_frame().
+// RANSAC state of one context (ransac.hip), carved from its RANSAC scratch by ransac_frame() (solve.h).
 struct RansacDev {
     int* rng;          // [34] glibc state (persistent)
     int* counts;       // [kHypMax]
@@ -441,52 +441,10 @@ constexpr int kPass1Fallback = 64;     // k_project_lane fallback blocks (one sl
 void launch_project_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp, int it,
                           int use_prev);
 
-// solve.hip
-void launch_solve_chain(hipStream_t s, int N, int blocks1, const KParams& kp, const float4* cs,
-                        const float4* cd, const float4* cn, const double* rows_d, const double* weights,
-                        SolveState& st, imls_iter_trace* tr, int update_pose, int rows_are_double,
-                        const int* count = nullptr, const double* wsum = nullptr);
-// N above which the float-row LS takes the grid chain (below: one block, k_solve_small)
+// sizes of the solve chain that the projection and the API read (the solver's launchers: solve.h)
 constexpr int kQwaveAutoN = 16384;  // auto traversal choice: one wave per query up to this many queries
-constexpr int kSmallRows = 4096;
-int solve_blocks(int N);
-// Batched LS / weighted-LS solve + pose update for all frames of tab (float rows from the batched
-// projection): k_solve_small over the frames with N ≤ kSmallRows, the grid chain over the others.
-// src 0: float rows of the batched projection; src 1: every frame's RANSAC inlier rows (fp64, the
-// grid chain always; n_host = the frames' RANSAC caps), pass 1 included.
-void launch_solve_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp, int it,
-                        int src = 0);
-// pass 1 over every frame's RANSAC inlier rows (weighted: w / Σw)
-void launch_rows_pass1_batch(hipStream_t s, const PairDev* tab, const int* cap_host, int npairs, int weighted);
-
-// solve_robust.hip — the robust M-estimator solve (IMLS_SOLVE_ROBUST): K re-weighted 6×6 solves of
-// the point-to-plane rows under ψ ∈ {Huber, Cauchy, Geman-McClure}, then Δ and the pose update.
-// Float rows of ≤ kSmallRows: one block; larger frames and fp64 rows: K × (grid pass, one-block solve).
-struct SolveLaunch;
-void launch_solve_robust(hipStream_t s, const SolveLaunch& L);
-// every frame of tab (float rows of the batched projection), one launch per step for the whole batch
-void launch_solve_robust_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp, int it);
-
-// pose_info.hip — the covariance / degeneracy report of the last solve (imls_capture_pose_info)
-struct InfoLaunch {
-    const float4 *cs, *cd, *cn;        // float rows of the projection, or
-    const double* rows_d;              // fp64 rows [s 3n | d 3n | n 3n] (weights, count, wsum as Rows takes them)
-    const double* weights;
-    const int* count;
-    const double* wsum;
-    int N;                             // rows to visit
-    const InfoExport* ex;
-    const int *status, *iters;         // the frame's (SolveState)
-    int in_loop;                       // a registration (its iteration must be the frame's last)
-    int solve_method, final_method;
-    int robust_loss;                   // ψ of a robust solve's weights (kInfoRobust)
-    double robust_scale;
-    double* slabs;                     // [info_blocks(N) × kInfoTerms]
-    struct imls_pose_info* out;               // device
-};
-constexpr int kInfoTerms = 32;         // 21 H + 6 g + btb + Σw + rows + rss (+ 1 unused)
-inline int info_blocks(int N) { return (std::max(N, 1) + kBlock - 1) / kBlock; }
-void launch_pose_info(hipStream_t s, const InfoLaunch& L);
+constexpr int kSmallRows = 4096;    // float-row frames up to this are solved by one block (k_solve_small)
+__host__ __device__ __forceinline__ int solve_blocks(int N) { return (N + kBlock - 1) / kBlock; }   // row blocks of the grid chain
 
 // normals.hip — map normals recomputed from the map (get_normals=false, count mode), Morton order
 int launch_map_normals(hipStream_t s, const TreeView& t, int K, double r_normal, float4* out);
@@ -500,40 +458,6 @@ void launch_tensor_gather(hipStream_t s, const float* ten6_in, size_t n_in, cons
                           float4* mten);
 void launch_tv_vote_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp,
                           int use_prev);
-
-// ransac.hip — RANSAC (+ final LS / weighted LS / DRPM) and the solve-method dispatcher
-constexpr int kHypMax = 8192;          // hypotheses per chunk (chunks: 16, then up to kHypMax each)
-struct RansacParams {
-    int max_iterations;
-    double distance_threshold, min_inliers_percentage, huber_threshold;
-    int final_method;                  // imls_final_method
-    double ls_threshold, drpm_threshold, drpm_stdev_points, drpm_stdev_normals;
-};
-struct SolveLaunch {
-    int N;                             // rows (float rows: source count; fp64 rows: row count)
-    int blocks1;                       // pass-1 slabs already in st.partial1 (float rows from k_finish)
-    KParams kp;
-    const float4 *cs, *cd, *cn;
-    const double* rows_d;              // fp64 rows [s 3N | d 3N | n 3N] (host API) or null
-    const double* weights;
-    SolveState st;
-    imls_iter_trace* tr;
-    int update_pose, rows_are_double;
-    const int* count;
-    void* scratch;                     // ransac_bytes(N) device bytes (RANSAC only)
-    int* rng;                          // [34] glibc rand() state, device (RANSAC only)
-    RansacParams ransac;
-};
-void launch_solve(hipStream_t s, const SolveLaunch& L);
-size_t ransac_bytes(int cap);
-RansacFrame ransac_frame(void* scratch, int cap, int* rng);   // the carve of ransac_bytes(cap)
-int ransac_init_tables(int device);    // the rand() jump table on `device` (current), once per device
-constexpr int kMaxRansacBatch = 1024;  // frames per batched RANSAC launch
-// Batched RANSAC (+ final LS / weighted LS / DRPM) for all frames of tab, ICP iteration `it`:
-// one launch per step for the whole batch, every frame at its own count / rand() stream / done flag.
-int launch_ransac_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp,
-                         const RansacParams& rp, int it);
-void ransac_seed_host(uint32_t seed, int st[34]);
 
 // Transfer accounting of a producer call (imls_sweep_info): bytes copied each way and host waits.
 struct Xfer {

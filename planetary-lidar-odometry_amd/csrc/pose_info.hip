@@ -17,6 +17,7 @@
 //   k_info_final  one block: the slabs summed in order (thread t takes slabs t, t + 256, …), H
 //                 mirrored, the DRPM head's Jacobi (sym_eig6_wave, solve_common.h: the same
 //                 operations and stop rule), the sign rule, rank, σ², the pseudo-inverse covariance.
+#include "solve.h"
 #include "solve_common.h"
 
 namespace imlsgpu {

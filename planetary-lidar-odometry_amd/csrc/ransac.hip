@@ -1,12 +1,11 @@
 // ransac.hip — SolveMotionEstimationProblemRANSAC (solver.cpp:222-385) with farthestPointSampling
-// (common.cpp:19-82) and SolveMotionEstimationProblemDRPM (solver.cpp:486-603, degeneracy.h:14-131)
-// on device, plus the solve-method dispatcher used by the ICP loop.
+// (common.cpp:19-82) on device.  The row compaction is compact_rows.hip, the DRPM final drpm.hip.
 //
 // Data flow per RANSAC solve (all on the context's stream, no host sync):
 //   1. the valid correspondences (float rows, source order) are compacted, order kept, into fp64
 //      rows S/D/N — the reference's std::vector<Vector3d> inputs; the TOO_FEW gate
 //      (laser_odometry.cpp:570-576) runs on their count;
-//   2. hypotheses in chunks (16, then up to kHypMax): k_ransac_hyp runs one hypothesis per block at
+//   2. hypotheses in chunks (ransac_chunks): k_ransac_hyp runs one hypothesis per block at
 //      a time — its glibc rand() draw (the FPS start index) by the jump table below, FPS (two
 //      arg-max passes, first index wins ties as the sequential `>` does), the 3×6 column-pivoted
 //      Householder QR basic solution (Eigen ColPivHouseholderQR, not normal equations: a rank-3
@@ -17,18 +16,19 @@
 //      w = √a < h₂ ? a : 2h₂√a − h₂², a = e^{−|r|}, h₂ = huber·distance (solver.cpp:334-356),
 //      normalised by Σw (361-364; the division happens where the weight is read);
 //   4. final solve: LS (trimmed, RANSAC's own threshold) / weighted LS through the LS chain on the
-//      fp64 inlier rows, or DRPM: H = Σ w a aᵀ and g = Σ w a b (pass 1 of the LS chain), a cyclic
-//      Jacobi eigendecomposition (SelfAdjointEigenSolver order: ascending), the per-point noise
-//      mean/variance along the eigenvectors, normal-CDF probabilities with SNR factor 10, and
-//      x = U·diag(p/λ)·Uᵀ g when min p < threshold, else the weighted solve.
+//      fp64 inlier rows, or DRPM (launch_drpm).
 // Batched frames (imls_register_frames, launch_ransac_batch): every step above is one launch for
 // all frames (grid y = frame, the same bodies; each frame keeps its own count, rand() stream, chunk
 // progress and done flag).
+// The rand() jump table is a __device__ variable, which belongs to one unit (the library is built
+// without relocatable device code): its readers — the hypothesis kernels, the select kernels and
+// k_drpm_head_small, which runs the select body — live here, as does the debug build's g_dbg_ransac.
 #include <algorithm>
 #include <mutex>
 #include <vector>
 
-#include "solve_common.h"
+#include "compact_rows.h"
+#include "drpm_common.h"
 
 namespace imlsgpu {
 namespace {
@@ -40,7 +40,6 @@ constexpr int kHypSmallRows = 4096;
 __host__ __device__ constexpr int hyp_block_of(int cap) { return cap <= kHypSmallRows ? 64 : 256; }
 constexpr int kHypUnroll = 8;        // FPS passes: rows per thread whose loads are in flight together
 constexpr int kHypGrid = 8192;        // batched hypothesis grid (blocks stride over the running frames' items)
-constexpr int kDrpmSlab = 42;         // 36 noise-mean terms + 6 variance terms per block
 #ifdef IMLS_DEBUG_WAVE_TRACE
 // phase clocks (100 MHz ticks) of block 0's hypothesis [0..5] and of k_drpm_head_small [8..13];
 // [6], [14]: call counts (tools/ransac_probe.py with the debug build)
@@ -95,323 +94,13 @@ __device__ __forceinline__ void rand_commit(int* __restrict__ st, int used) {
     if (lane == 0) { st[31] = (f + used) % 31; st[32] = (r + used) % 31; }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Order-keeping compaction (count → scan → scatter) into fp64 row arrays of stride `cap`
-// ---------------------------------------------------------------------------------------------
-struct CompactOut {
-    double* rows;       // [10·cap]: s[3·cap] | d[3·cap] | n[3·cap] (xyz per row) | w[cap] — the Rows layout
-    int* count;         // [1]
-    double* wsum;       // [1] Σw of the kept rows (inlier pass) — may be null
-    int cap;
-};
-
-// Predicate + payload: valid correspondences of the projection (float rows), or inliers of Δ.
-struct Source {
-    const float4 *cs, *cd, *cn;       // float rows (valid flag cs.w), or null
-    const double* rows;               // fp64 rows (Rows layout, stride cap) with count, or null
-    const int* count;
-    int cap;
-    const double* T;                  // inlier pass: Δ (row-major 4×4)
-    double dist_thr, h2;
-    __device__ __forceinline__ bool get(int i, double s[3], double d[3], double n[3], double& w) const {
-        if (cs) {
-            const float4 s4 = cs[i];
-            if (s4.w == 0.f) return false;
-            const float4 d4 = cd[i], n4 = cn[i];
-            s[0] = s4.x; s[1] = s4.y; s[2] = s4.z;
-            d[0] = d4.x; d[1] = d4.y; d[2] = d4.z;
-            n[0] = n4.x; n[1] = n4.y; n[2] = n4.z;
-            w = 1.0;
-            return true;
-        }
-        if (i >= *count) return false;
-        const size_t c3 = 3 * (size_t)cap;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            s[k] = rows[3 * (size_t)i + k];
-            d[k] = rows[c3 + 3 * (size_t)i + k];
-            n[k] = rows[2 * c3 + 3 * (size_t)i + k];
-        }
-        if (!T) { w = 1.0; return true; }
-        // solver.cpp:301-314 / 334-356: point-to-plane distance of Δ·s
-        double tp[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) tp[r] = ((T[r * 4] * s[0] + T[r * 4 + 1] * s[1]) + T[r * 4 + 2] * s[2]) + T[r * 4 + 3];
-        const double dist = fabs(((tp[0] - d[0]) * n[0] + (tp[1] - d[1]) * n[1]) + (tp[2] - d[2]) * n[2]);
-        if (!(dist < dist_thr)) return false;
-        const double ar = exp(-fabs(dist));
-        w = sqrt(ar) < h2 ? ar : 2 * h2 * sqrt(ar) - h2 * h2;
-        return true;
-    }
-};
-
-__device__ __forceinline__ void compact_count_body(const Source& src, int n, int* __restrict__ blkcnt,
-                                                   double* __restrict__ blkw) {
-    __shared__ int wc[kBlock / 64];
-    __shared__ double ws[kBlock / 64];
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    double s[3], d[3], nn[3], w = 0.0;
-    const bool keep = i < n && src.get(i, s, d, nn, w);
-    const unsigned long long m = __ballot(keep);
-    const double wv = wave_sum(keep ? w : 0.0);
-    if ((threadIdx.x & 63) == 0) { wc[threadIdx.x >> 6] = __popcll(m); ws[threadIdx.x >> 6] = wv; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int c = 0;
-        double sw = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) { c += wc[k]; sw += ws[k]; }
-        blkcnt[blockIdx.x] = c;
-        blkw[blockIdx.x] = sw;
-    }
-}
-
-// What runs after a compaction, by thread 0 with the kept count (one launch fewer each): the RANSAC
-// begin (the TOO_FEW gate, laser_odometry.cpp:570-576, and the selection reset) after the valid-row
-// compaction; the empty-inlier check after the inlier one.
-struct CompactPost {
-    int kind;                         // 0 none, 1 RANSAC begin, 2 inlier check
-    int correspond_number, update_pose;
-    SolveState st;
-    imls_iter_trace* tr;
-    RansacDev R;
-};
-__device__ __forceinline__ void ransac_begin_t0(int n, int correspond_number, int update_pose, const SolveState& st,
-                                                imls_iter_trace* tr, const RansacDev& R) {
-    *R.active = 1;
-    if (update_pose && n < correspond_number) {
-        *st.status = IMLS_FRAME_TOO_FEW;
-        *st.done = 1;
-        if (tr) tr->n_valid = (unsigned long long)n;
-        return;
-    }
-    *R.best = 0;
-    *R.evaluated = 0;
-    *R.rdone = n < 3 ? 1 : 0;   // FPS needs three distinct points
-#pragma unroll
-    for (int k = 0; k < 16; ++k) R.bestT[k] = (k % 5 == 0) ? 1.0 : 0.0;
-}
-__device__ __forceinline__ void compact_post(const CompactPost& P, int n) {
-    if (P.kind == 1) {
-        ransac_begin_t0(n, P.correspond_number, P.update_pose, P.st, P.tr, P.R);
-    } else if (P.kind == 2 && n == 0) {   // nothing to solve on (the oracle's N == 0 → false): a failed solve
-        *P.st.status = IMLS_FRAME_SOLVE_FAILED;
-        *P.st.done = 1;
-    }
-}
-// a finished frame skips the compaction; its RANSAC solve is then inactive (no trace record)
-__device__ __forceinline__ bool compact_skip(const CompactPost& P) {
-    if (!*P.st.done) return false;
-    if (P.kind == 1 && threadIdx.x == 0) *P.R.active = 0;
-    return true;
-}
-
-// One block: exclusive scan of the block counts (in place), total count and Σw in fixed order.
-__device__ __forceinline__ void compact_scan_body(int* __restrict__ blkcnt, const double* __restrict__ blkw, int nb,
-                                                  const CompactOut& out, const CompactPost& P) {
-    __shared__ int sc[1024];
-    __shared__ double sw[1024];
-    int carry = 0;
-    double wcarry = 0.0;
-    for (int base = 0; base < nb; base += 1024) {
-        const int b = base + threadIdx.x;
-        const int v = b < nb ? blkcnt[b] : 0;
-        sc[threadIdx.x] = v;
-        sw[threadIdx.x] = b < nb ? blkw[b] : 0.0;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int t = threadIdx.x >= off ? sc[threadIdx.x - off] : 0;
-            __syncthreads();
-            sc[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (b < nb) blkcnt[b] = carry + sc[threadIdx.x] - v;
-        if (threadIdx.x == 0) {
-            double acc = 0.0;
-            for (int k = 0; k < 1024 && base + k < nb; ++k) acc += sw[k];
-            sw[0] = acc;   // reuse after the scan: chunk sum
-        }
-        __syncthreads();
-        carry += sc[1023];
-        wcarry += sw[0];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *out.count = carry;
-        if (out.wsum) *out.wsum = wcarry;
-        compact_post(P, carry);
-    }
-}
-
-// The whole compaction in one 1024-thread block (count + scan + scatter, for caps ≤ kCompactOne):
-// tiles of 1024 rows in order; Σw accumulated exactly as the three-kernel path does it (per-wave
-// sums, 4 waves per 256-row block in order, then the block sums in block order) — same bits.
-constexpr int kCompactOne = 16384;
-__device__ __forceinline__ void compact_one_body(const Source& src, int n, const CompactOut& out, const CompactPost& P) {
-    __shared__ int wc[16];
-    __shared__ double ws[16];
-    __shared__ int sbase;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    if (t == 0) sbase = 0;
-    double wacc = 0.0;                                     // thread 0
-    for (int tile = 0; tile < n; tile += 1024) {
-        const int i = tile + t;
-        double s[3], d[3], nn[3], w = 0.0;
-        const bool keep = i < n && src.get(i, s, d, nn, w);
-        const unsigned long long m = __ballot(keep);
-        const double wvs = wave_sum(keep ? w : 0.0);
-        if (lane == 0) { wc[wv] = __popcll(m); ws[wv] = wvs; }
-        __syncthreads();
-        int off = sbase;
-        for (int k = 0; k < wv; ++k) off += wc[k];
-        off += __popcll(m & ((1ull << lane) - 1ull));
-        if (keep) {
-            const size_t c3 = 3 * (size_t)out.cap, o = (size_t)off;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                out.rows[3 * o + k] = s[k];
-                out.rows[c3 + 3 * o + k] = d[k];
-                out.rows[2 * c3 + 3 * o + k] = nn[k];
-            }
-            out.rows[3 * c3 + o] = w;
-        }
-        __syncthreads();
-        if (t == 0) {
-            int tot = 0;
-            for (int b = 0; b < 4; ++b) {
-                if (tile + 256 * b >= n) break;            // blocks past n do not exist in the 3-kernel path
-                double sw = 0.0;
-                for (int k = 0; k < 4; ++k) { sw += ws[4 * b + k]; tot += wc[4 * b + k]; }
-                wacc += sw;
-            }
-            sbase += tot;
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        *out.count = sbase;
-        if (out.wsum) *out.wsum = wacc;
-        compact_post(P, sbase);
-    }
-}
-
-__device__ __forceinline__ void compact_scatter_body(const Source& src, int n, const int* __restrict__ blkoff,
-                                                     const CompactOut& out) {
-    __shared__ int wc[kBlock / 64];
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double s[3], d[3], nn[3], w = 0.0;
-    const bool keep = i < n && src.get(i, s, d, nn, w);
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) wc[wv] = __popcll(m);
-    __syncthreads();
-    int off = blkoff[blockIdx.x];
-    for (int k = 0; k < wv; ++k) off += wc[k];
-    off += __popcll(m & ((1ull << lane) - 1ull));
-    if (keep) {
-        const size_t c3 = 3 * (size_t)out.cap, o = (size_t)off;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            out.rows[3 * o + k] = s[k];
-            out.rows[c3 + 3 * o + k] = d[k];
-            out.rows[2 * c3 + 3 * o + k] = nn[k];
-        }
-        out.rows[3 * c3 + o] = w;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_compact_count(Source src, int n, int* __restrict__ blkcnt,
-                                                          double* __restrict__ blkw, const int* __restrict__ done) {
-    if (done && *done) return;
-    compact_count_body(src, n, blkcnt, blkw);
-}
-__global__ __launch_bounds__(1024) void k_compact_scan(int* __restrict__ blkcnt, const double* __restrict__ blkw, int nb,
-                                                       CompactOut out, CompactPost P) {
-    if (compact_skip(P)) return;
-    compact_scan_body(blkcnt, blkw, nb, out, P);
-}
-__global__ __launch_bounds__(1024) void k_compact_one(Source src, int n, CompactOut out, CompactPost P) {
-    if (compact_skip(P)) return;
-    compact_one_body(src, n, out, P);
-}
-__global__ __launch_bounds__(kBlock) void k_compact_scatter(Source src, int n, const int* __restrict__ blkoff, CompactOut out,
-                                                            const int* __restrict__ done) {
-    if (done && *done) return;
-    compact_scatter_body(src, n, blkoff, out);
-}
-
-// The two compactions of a batched frame: mode 0 = its valid float rows (the projection's output)
-// → F.all; mode 1 = the inliers of its best Δ, weighted → F.inl (+ Σw).
-__device__ __forceinline__ int frame_compact(const PairDev& A, int mode, double dist_thr, double h2, Source& src,
-                                             CompactOut& out) {
-    const RansacFrame& F = A.rf;
-    src = Source{};
-    if (mode == 0) {
-        src.cs = A.cs; src.cd = A.cd; src.cn = A.cn;
-        out = CompactOut{F.all, F.cnt_all, nullptr, F.cap};
-        return A.N;
-    }
-    src.rows = F.all; src.count = F.cnt_all; src.cap = F.cap; src.T = F.R.bestT;
-    src.dist_thr = dist_thr; src.h2 = h2;
-    out = CompactOut{F.inl, F.cnt_in, F.wsum, F.cap};
-    return F.cap;
-}
-__global__ __launch_bounds__(kBlock) void k_compact_count_b(const PairDev* __restrict__ tab, int mode, double dist_thr,
-                                                            double h2) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    Source src;
-    CompactOut out;
-    const int n = frame_compact(A, mode, dist_thr, h2, src, out);
-    if ((int)blockIdx.x >= (n + kBlock - 1) / kBlock || *A.st.done) return;
-    compact_count_body(src, n, A.rf.blkcnt, A.rf.blkw);
-}
-__device__ __forceinline__ CompactPost frame_post(const PairDev& A, int mode, int correspond_number, int it) {
-    return CompactPost{mode == 0 ? 1 : 2, correspond_number, 1, A.st, A.trace + it, A.rf.R};
-}
-__global__ __launch_bounds__(1024) void k_compact_scan_b(const PairDev* __restrict__ tab, int mode, int correspond_number,
-                                                         int it) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    const CompactPost P = frame_post(A, mode, correspond_number, it);
-    if (compact_skip(P)) return;
-    Source src;
-    CompactOut out;
-    const int n = frame_compact(A, mode, 0.0, 0.0, src, out);
-    compact_scan_body(A.rf.blkcnt, A.rf.blkw, (n + kBlock - 1) / kBlock, out, P);
-}
-__global__ __launch_bounds__(1024) void k_compact_one_b(const PairDev* __restrict__ tab, int mode, double dist_thr, double h2,
-                                                        int correspond_number, int it) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    const CompactPost P = frame_post(A, mode, correspond_number, it);
-    if (compact_skip(P)) return;
-    Source src;
-    CompactOut out;
-    const int n = frame_compact(A, mode, dist_thr, h2, src, out);
-    compact_one_body(src, n, out, P);
-}
-__global__ __launch_bounds__(kBlock) void k_compact_scatter_b(const PairDev* __restrict__ tab, int mode, double dist_thr,
-                                                              double h2) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    Source src;
-    CompactOut out;
-    const int n = frame_compact(A, mode, dist_thr, h2, src, out);
-    if ((int)blockIdx.x >= (n + kBlock - 1) / kBlock || *A.st.done) return;
-    compact_scatter_body(src, n, A.rf.blkcnt, out);
-}
-
-// stand-alone DRPM with no rows fails like the oracle's solve_drpm (N == 0 → false)
-__global__ void k_drpm_guard(const int* __restrict__ c, SolveState st) {
-    if (threadIdx.x == 0 && *c == 0) { *st.status = IMLS_FRAME_SOLVE_FAILED; *st.done = 1; }
-}
-
-__global__ void k_set_count(int* __restrict__ c, int v) {
-    if (threadIdx.x == 0) *c = v;
-}
-
-// gate on the count, reset the RANSAC selection state (host fp64 rows, no compaction to fold it into)
+// the valid-row compaction's post step on its own (host fp64 rows arrive compact): the gate on the
+// count and the reset of the selection state
 __global__ void k_ransac_begin(const int* __restrict__ count, int correspond_number, int update_pose, SolveState st,
                                imls_iter_trace* tr, RansacDev R) {
-    if (threadIdx.x) return;
-    if (*st.done) { *R.active = 0; return; }
-    ransac_begin_t0(*count, correspond_number, update_pose, st, tr, R);
+    const CompactPost P{1, correspond_number, update_pose, st, tr, R};
+    if (threadIdx.x || compact_skip(P)) return;
+    compact_post(P, *count);
 }
 
 // block arg-max of (value, index): larger value, then smaller index
@@ -786,301 +475,25 @@ __global__ __launch_bounds__(64) void k_ransac_select(const int* __restrict__ co
     ransac_select_body(count, R, chunk, max_iterations, min_pct);
 }
 
-// trace of a RANSAC iteration as the oracle records it: n_valid = correspondences, n_kept = 0
+// RANSAC's own trace record behind an LS / weighted-LS final (the DRPM final writes it itself).
+// Launched only with a trace slot: the body's null test (the stand-alone DRPM's) folds away.
 __global__ void k_ransac_trace(const int* __restrict__ count_all, RansacDev R, imls_iter_trace* tr) {
-    if (threadIdx.x || !*R.active || !tr) return;
-    tr->n_valid = (unsigned long long)*count_all;
-    tr->n_kept = 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// DRPM (solver.cpp:499-603, degeneracy.h:14-131)
-// ---------------------------------------------------------------------------------------------
-// The wave's totals of the 42 DRPM terms by recursive halving (internal.h wave_sum28's scheme): terms
-// 0..31 in one pass (31 + 1 fp64 exchanges), 32..41 padded to 16 in another (15 + 2) — 49 exchanges
-// where 42 butterfly wave_sums issued 252 (round 6).  Lane 2k returns total k in r0 (k < 32) and
-// total 32 + k in r1 (k < 10).  A fixed association shared by every DRPM launch (alone and batched).
-template <int H, int N>
-__device__ __forceinline__ void halve_n(double (&a)[N], int lane) {
-    const bool up = (lane & (2 * H)) != 0;
-#pragma unroll
-    for (int i = 0; i < H; ++i) {
-        const double send = up ? a[i] : a[H + i];
-        const double keep = up ? a[H + i] : a[i];
-        a[i] = keep + xor_f64(send, 2 * H);
-    }
-    if constexpr (H > 1) halve_n<H / 2, N>(a, lane);
-}
-__device__ __forceinline__ void wave_sum42(const double (&v)[kDrpmSlab], double& r0, double& r1) {
-    const int lane = threadIdx.x & 63;
-    double a[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) a[k] = v[k];
-    halve_n<16, 32>(a, lane);
-    r0 = a[0] + xor_f64(a[0], 1);
-    double b[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) b[k] = k < kDrpmSlab - 32 ? v[32 + k] : 0.0;
-    halve_n<8, 16>(b, lane);
-    r1 = b[0] + xor_f64(b[0], 1);
-    r1 = r1 + xor_f64(r1, 32);
-}
-// lane 2k of wave wv writes its totals to red[wv][·] (the block's per-wave rows)
-__device__ __forceinline__ void wave_sum42_store(const double (&v)[kDrpmSlab], double* __restrict__ row) {
-    double r0, r1;
-    wave_sum42(v, r0, r1);
-    const int lane = threadIdx.x & 63;
-    if (!(lane & 1)) {
-        row[lane >> 1] = r0;
-        if ((lane >> 1) < kDrpmSlab - 32) row[32 + (lane >> 1)] = r1;
-    }
-}
-
-// reduce the weighted normal equations (pass-1 slabs), eigendecompose H
-__device__ __forceinline__ void drpm_eig_body(const double* __restrict__ partial, int blocks, const SolveState& st,
-                                              const DrpmDev& Dv) {
-    if (*st.done) return;
-    __shared__ double red[(256 / 64) * kNormEq];
-    __shared__ double acc[kNormEq];
-    double loc[kNormEq];
-#pragma unroll
-    for (int k = 0; k < kNormEq; ++k) loc[k] = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += 256)
-#pragma unroll
-        for (int k = 0; k < kNormEq; ++k) loc[k] += partial[(size_t)b * kNormEq + k];
-    block_sum28<256>(loc, red, acc);
-    if (threadIdx.x >= 64) return;
-    // H (row-major, from the upper-triangle terms) and g; the eigendecomposition by wave 0, lane k
-    // holding row k (sym_eig6_wave: the oracle's Jacobi, operation for operation)
-    const int lane = threadIdx.x, k = lane < 6 ? lane : 0;
-    double row[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int r0 = k < c ? k : c, c0 = k < c ? c : k;
-        row[c] = acc[6 * r0 - r0 * (r0 - 1) / 2 + (c0 - r0)];
-    }
-    if (lane < 6) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) Dv.H[lane * 6 + c] = row[c];
-        Dv.g[lane] = acc[21 + lane];
-    }
-    sym_eig6_wave(row, Dv.ev, Dv.U);
-}
-
-// the 42 noise terms of row i (zero when i ≥ N or the row is absent), degeneracy.h:14-72
-__device__ __forceinline__ void drpm_noise_terms(const Rows& rows, int i, int N, const DrpmDev& Dv, double sp, double sn,
-                                                 double (&acc)[kDrpmSlab]) {
-#pragma unroll
-    for (int k = 0; k < kDrpmSlab; ++k) acc[k] = 0.0;
-    double a[6], b, wt;
-    if (i < N && rows.get(i, a, b, wt)) {
-        const size_t i3 = 3 * (size_t)i;
-        const double s[3] = {rows.ds[i3], rows.ds[i3 + 1], rows.ds[i3 + 2]};
-        const double n[3] = {rows.dn[i3], rows.dn[i3 + 1], rows.dn[i3 + 2]};
-        // skew(v) = [0 −z y; z 0 −x; −y x 0] (degeneracy.h:7-12)
-        const double nx[9] = {0, -n[2], n[1], n[2], 0, -n[0], -n[1], n[0], 0};
-        const double px[9] = {0, -s[2], s[1], s[2], 0, -s[0], -s[1], s[0], 0};
-        double B[36];
-#pragma unroll
-        for (int q = 0; q < 36; ++q) B[q] = 0.0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                B[r * 6 + c] = -nx[r * 3 + c];
-                double pn = 0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) pn += px[r * 3 + k] * nx[k * 3 + c];
-                B[r * 6 + 3 + c] = pn;
-                B[(3 + r) * 6 + 3 + c] = nx[r * 3 + c];
-            }
-        const double sp2 = sp * sp, sn2 = sn * sn;
-        const double Nd[6] = {sp2, sp2, sp2, sn2, sn2, sn2};
-        double C[36];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                double v = 0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) v += B[r * 6 + k] * Nd[k] * B[c * 6 + k];
-                C[r * 6 + c] = v * wt;
-            }
-#pragma unroll
-        for (int q = 0; q < 36; ++q) acc[q] = C[q];
-        const double sw = sqrt(wt);
-        double v6[6];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            double pn = 0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pn += px[r * 3 + k] * n[k];
-            v6[r] = sw * pn;
-            v6[3 + r] = sw * n[r];
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            double aa = 0, bb = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                double cu = 0;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) cu += C[r * 6 + c] * Dv.U[k * 6 + c];
-                aa += Dv.U[k * 6 + r] * cu;
-                bb += Dv.U[k * 6 + r] * v6[r];
-            }
-            acc[36 + k] = 2 * aa * aa + 4 * aa * bb * bb;
-        }
-    }
-}
-
-// per-point noise mean (36) and variance along the eigenvectors (6), degeneracy.h:14-72
-__device__ __forceinline__ void drpm_noise_body(const Rows& rows, int N, const SolveState& st, const DrpmDev& Dv, double sp,
-                                                double sn) {
-    if (*st.done) return;
-    __shared__ double red[(kBlock / 64) * kDrpmSlab];
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    double acc[kDrpmSlab];
-    drpm_noise_terms(rows, i, N, Dv, sp, sn, acc);
-    const int wv = threadIdx.x >> 6;
-    wave_sum42_store(acc, red + wv * kDrpmSlab);
-    __syncthreads();
-    if (threadIdx.x < kDrpmSlab) {
-        double s = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) s += red[w * kDrpmSlab + threadIdx.x];
-        Dv.slabs[(size_t)blockIdx.x * kDrpmSlab + threadIdx.x] = s;
-    }
-}
-
-__device__ __forceinline__ double normal_cdf(double mean, double sd, double x) {
-    return 0.5 * erfc(-(x - mean) / (sd * sqrt(2.0)));   // Boost.Math cdf(normal(mean, sd), x)
-}
-
-// The DRPM decision and solve from the reduced noise terms tot[42] (solver.cpp:540-603), by wave 0
-// (every other thread returns): lane k < 6 evaluates prob[k] — the thread-0 loop's expressions for
-// that k, so the same bits — the minimum over k in order, then either the SNR-weighted
-// eigen-solution (thread 0) or the plain normal-equation solve by the whole wave (solve6_u: solve6's
-// operations with a wave-uniform pivot, bit for bit), Δ and the pose update by thread 0.  Round 6:
-// one thread ran all six probabilities and solve6's predicated pivot swaps (k_drpm_final 27 µs per
-// call on a lone 1600-row frame, profiles/r06_calib).
-__device__ __forceinline__ void drpm_solve_wave0(const SolveState& st, const DrpmDev& Dv, imls_iter_trace* tr,
-                                                 const KParams& kp, double threshold, const int* __restrict__ count_all,
-                                                 const int* __restrict__ count_in, int update_pose, const double* tot) {
-    if (threadIdx.x >= 64) return;
-    const int lane = threadIdx.x;
-    const double snr = 10.0;   // solver.cpp:547
-    double pk = 0.0;
-    if (lane < 6) {
-        const int k = lane;
-        double meas = 0, exp_noise = 0;
-        for (int r = 0; r < 6; ++r) {
-            double hu = 0, mu = 0;
-            for (int c = 0; c < 6; ++c) { hu += Dv.H[r * 6 + c] * Dv.U[k * 6 + c]; mu += tot[r * 6 + c] * Dv.U[k * 6 + c]; }
-            meas += Dv.U[k * 6 + r] * hu;
-            exp_noise += Dv.U[k * 6 + r] * mu;
-        }
-        const double sd = sqrt(tot[36 + k]);
-        const double tp = meas / (1.0 + snr);
-        const bool bad = isnan(exp_noise) || isnan(sd) || isnan(tp);
-        pk = bad ? 0.0 : normal_cdf(exp_noise, sd, tp);
-    }
-    double prob[6], pmin = INFINITY;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        prob[k] = readlane_f64(pk, k);
-        pmin = fmin(pmin, prob[k]);
-    }
-    double x[6];
-    if (pmin < threshold) {
-        if (lane) return;
-        double ut[6];
-        for (int k = 0; k < 6; ++k) {
-            const double dps = fabs(Dv.ev[k]) > 1e-10 ? prob[k] / Dv.ev[k] : 0.0;
-            double acc = 0;
-            for (int r = 0; r < 6; ++r) acc += Dv.U[k * 6 + r] * Dv.g[r];
-            ut[k] = dps * acc;
-        }
-        for (int r = 0; r < 6; ++r) {
-            double acc = 0;
-            for (int k = 0; k < 6; ++k) acc += Dv.U[k * 6 + r] * ut[k];
-            x[r] = acc;
-        }
-    } else {
-        double ne[kNormEq];
-        int k = 0;
-        for (int r = 0; r < 6; ++r)
-            for (int c = r; c < 6; ++c) ne[k++] = Dv.H[r * 6 + c];
-        for (int r = 0; r < 6; ++r) ne[21 + r] = Dv.g[r];
-        ne[27] = 0;
-        solve6_u(ne, x);
-        if (lane) return;
-    }
-    double D[16];
-    delta_from_x(x, D);
-    finish_iteration(st, tr, D, (double)*count_all, (double)*count_in, update_pose, kp);
-    if (st.info) {
-        for (int k = 0; k < 6; ++k) st.info->prob[k] = prob[k];
-        st.info->degenerate = pmin < threshold ? 1 : 0;
-        info_export(st.info, kInfoDrpm, x, st, update_pose);
-    }
-}
-
-__device__ __forceinline__ void drpm_final_body(int blocks, const SolveState& st, const DrpmDev& Dv, imls_iter_trace* tr,
-                                                const KParams& kp, double threshold, const int* __restrict__ count_all,
-                                                const int* __restrict__ count_in, int update_pose) {
-    if (*st.done) return;
-    __shared__ double red[(256 / 64) * kDrpmSlab];
-    __shared__ double tot[kDrpmSlab];
-    double loc[kDrpmSlab];
-#pragma unroll
-    for (int k = 0; k < kDrpmSlab; ++k) loc[k] = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += 256)
-#pragma unroll
-        for (int k = 0; k < kDrpmSlab; ++k) loc[k] += Dv.slabs[(size_t)b * kDrpmSlab + k];
-    const int wv = threadIdx.x >> 6;
-    wave_sum42_store(loc, red + wv * kDrpmSlab);
-    __syncthreads();
-    if (threadIdx.x < kDrpmSlab) {
-        double s = 0.0;
-        for (int w = 0; w < 256 / 64; ++w) s += red[w * kDrpmSlab + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-    drpm_solve_wave0(st, Dv, tr, kp, threshold, count_all, count_in, update_pose, tot);
-}
-
-__global__ __launch_bounds__(256) void k_drpm_eig(const double* __restrict__ partial, int blocks, SolveState st, DrpmDev Dv) {
-    drpm_eig_body(partial, blocks, st, Dv);
-}
-__global__ __launch_bounds__(kBlock) void k_drpm_noise(Rows rows, int N, SolveState st, DrpmDev Dv, double sp, double sn) {
-    drpm_noise_body(rows, N, st, Dv, sp, sn);
-}
-// rtr: RANSAC's own trace record (n_valid = correspondences, n_kept = 0) when the solve was active,
-// written after the final solve's; null for the stand-alone DRPM
-__device__ __forceinline__ void ransac_trace_t0(const RansacDev& R, const int* __restrict__ count_all, imls_iter_trace* rtr) {
-    if (threadIdx.x == 0 && rtr && *R.active) {
-        rtr->n_valid = (unsigned long long)*count_all;
-        rtr->n_kept = 0;
-    }
-}
-__global__ __launch_bounds__(256) void k_drpm_final(int blocks, SolveState st, DrpmDev Dv, imls_iter_trace* tr, KParams kp,
-                                                    double threshold, const int* __restrict__ count_all,
-                                                    const int* __restrict__ count_in, int update_pose, RansacDev R,
-                                                    imls_iter_trace* rtr) {
-    drpm_final_body(blocks, st, Dv, tr, kp, threshold, count_all, count_in, update_pose);
-    ransac_trace_t0(R, count_all, rtr);
+    __builtin_assume(tr != nullptr);
+    ransac_trace_t0(R, count_all, tr);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The lone frame's DRPM head in ONE launch (round 6; frames of ≤ kSmallRows rows registered alone,
 // the config C/D deployment shape): the inlier compaction, pass 1 of the weighted normal equations
 // over the inliers and the eigendecomposition — three launches before (k_compact_one, k_rows_pass1,
-// k_drpm_eig) — preceded by the last hypothesis chunk's selection (k_ransac_select, round 6).  One 1024-thread block runs them between block barriers; pass 1 runs as "virtual
-// blocks" — block b of k_rows_pass1's grid is done by the 256-thread group (b mod 4) in round b / 4,
-// with the same thread ↔ row mapping, the same per-wave reductions and the same slab order, and the
-// slab sum by the first 256 threads as k_drpm_eig does it — so every value is the chain's bit for bit
-// (the batched frames keep the chain: alone and batched agree).  The noise terms and the solve stay
+// k_drpm_eig) — preceded by the last hypothesis chunk's selection (k_ransac_select, round 6).  One
+// 1024-thread block runs them between block barriers; pass 1 runs as "virtual blocks" — block b of
+// k_rows_pass1's grid is done by the 256-thread group (b mod 4) in round b / 4, with the same
+// thread ↔ row mapping, the same per-wave reductions and the same slab order, and the slab sum by
+// the first 256 threads as k_drpm_eig does it — so every value is the chain's bit for bit: the
+// row terms are block_normeq's (normeq_terms) and the H / g fill and the eigendecomposition are
+// k_drpm_eig's (drpm_eig_tail), the same code (the batched frames keep the chain: alone and batched
+// agree).  The noise terms and the solve stay
 // grid / one-block launches: fused into this block as well (virtual noise blocks, measured) the
 // frame's DRPM took 102.7 µs per ICP iteration against the chain's 70 (one CU for the noise phase,
 // its registers at 2 waves per SIMD; profiles/r06_ransac/).
@@ -1130,16 +543,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_drpm_head_small(SelectArgs sel
             cnt = 1;
         }
         double v[32];
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = r; c < 6; ++c) v[k++] = a[r] * a[c];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) v[21 + r] = a[r] * bb;
-        v[27] = cnt;
-#pragma unroll
-        for (int q = kNormEq; q < 32; ++q) v[q] = 0.0;
+        normeq_terms(a, bb, cnt, v);
         const double sum = wave_sum28(v);
         if (!(lane & 1) && (lane >> 1) < kNormEq) red_ne[wv][lane >> 1] = sum;
         __syncthreads();
@@ -1175,20 +579,8 @@ __global__ __launch_bounds__(kHeadThreads) void k_drpm_head_small(SelectArgs sel
     }
     __syncthreads();
     if (tid >= 64) return;
-    const int k = lane < 6 ? lane : 0;
-    double row[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int r0 = k < c ? k : c, c0 = k < c ? c : k;
-        row[c] = acc[6 * r0 - r0 * (r0 - 1) / 2 + (c0 - r0)];
-    }
-    if (lane < 6) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) Dv.H[lane * 6 + c] = row[c];
-        Dv.g[lane] = acc[21 + lane];
-    }
     RSTAMP(11);
-    const int sweeps = sym_eig6_wave(row, Dv.ev, Dv.U);
+    const int sweeps = drpm_eig_tail(acc, Dv);   // H, g, the eigendecomposition: k_drpm_eig's
     RSTAMP(12);
 #ifdef IMLS_DEBUG_WAVE_TRACE
     if (dbg_on) g_dbg_ransac[13] += (unsigned long long)sweeps;
@@ -1207,8 +599,8 @@ namespace {
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// Batched RANSAC / DRPM kernels (launch_ransac_batch): frame = tab[blockIdx.y], the same bodies as
-// the one-frame kernels above; the frame's RANSAC scratch is A.rf, its pose update always on.
+// Batched RANSAC kernels (launch_ransac_batch): frame = tab[blockIdx.y], the same bodies as the
+// one-frame kernels above; the frame's RANSAC scratch is A.rf, its pose update always on.
 // ---------------------------------------------------------------------------------------------
 // The chunk's hypotheses of the frames still running, spread evenly over the grid: each block first
 // lists the running frames (done / RANSAC-finished ones drop out), then strides over
@@ -1250,40 +642,20 @@ __global__ __launch_bounds__(64) void k_ransac_select_b(const PairDev* __restric
     if (*A.st.done || *A.rf.R.rdone) return;
     ransac_select_body(A.rf.cnt_all, A.rf.R, chunk, max_iterations, min_pct);
 }
-// trace of a RANSAC iteration as the oracle records it (n_valid = correspondences, n_kept = 0) —
-// LS / weighted-LS finals; the DRPM final writes it itself
 __global__ void k_ransac_trace_b(const PairDev* __restrict__ tab, int it) {
     const PairDev A = device_view(tab + blockIdx.y);
-    if (threadIdx.x || !*A.rf.R.active) return;
-    A.trace[it].n_valid = (unsigned long long)*A.rf.cnt_all;
-    A.trace[it].n_kept = 0;
-}
-__global__ __launch_bounds__(256) void k_drpm_eig_b(const PairDev* __restrict__ tab) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    drpm_eig_body(A.st.partial1, solve_blocks_of(A.rf.cap), A.st, A.rf.Dv);
-}
-__global__ __launch_bounds__(kBlock) void k_drpm_noise_b(const PairDev* __restrict__ tab, double sp, double sn) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    if ((int)blockIdx.x >= solve_blocks_of(A.rf.cap)) return;
-    drpm_noise_body(frame_rows(A, 1, 1), A.rf.cap, A.st, A.rf.Dv, sp, sn);
-}
-__global__ __launch_bounds__(256) void k_drpm_final_b(const PairDev* __restrict__ tab, KParams kp, double threshold, int it) {
-    const PairDev A = device_view(tab + blockIdx.y);
-    drpm_final_body(solve_blocks_of(A.rf.cap), A.st, A.rf.Dv, A.trace + it, kp, threshold, A.rf.cnt_all, A.rf.cnt_in, 1);
+    __builtin_assume(A.trace + it != nullptr);
     ransac_trace_t0(A.rf.R, A.rf.cnt_all, A.trace + it);
 }
 
-// chunk sizes of the hypothesis loop: 16 (the usual early exit: the shipped 95 % inlier bar is mostly
-// met by the first hypotheses), 256, then the rest in chunks of kHypMax — three chunks for
-// max_iterations ≤ kHypMax + 272.  (Results do not depend on the chunking: exactly the draws
-// consumed are committed.)
 // Hypothesis chunks.  Each hypothesis takes its own rand() word (the h-th ahead of the chunk's state)
 // and the select commits exactly the words used, so any chunking gives the same result; chunks only
-// trade wasted work after an early exit against launches.  Batched frames: 16, 256, then up to
-// kHypMax (throughput: a frame that exits early wastes little of the shared grid).  A frame alone
-// (lone = true, the deployment shape): 272, then up to kHypMax — the first two batched chunks in one
-// launch (both fit one wave of blocks, so the merged launch takes about as long as the 16; round 6:
-// a lone 1600-row frame without an early exit ran 3 hypothesis + 3 select launches per ICP iteration).
+// trade wasted work after an early exit against launches.  Batched frames: 16 (the usual early exit:
+// the shipped 95 % inlier bar is mostly met by the first hypotheses), 256, then up to kHypMax
+// (throughput: a frame that exits early wastes little of the shared grid).  A frame alone (lone =
+// true, the deployment shape): 272, then up to kHypMax — the first two batched chunks in one launch
+// (both fit one wave of blocks, so the merged launch takes about as long as the 16; round 6: a lone
+// 1600-row frame without an early exit ran 3 hypothesis + 3 select launches per ICP iteration).
 std::vector<int> ransac_chunks(int max_iterations, bool lone = false) {
     std::vector<int> v;
     for (int started = 0; started < max_iterations;) {
@@ -1295,76 +667,64 @@ std::vector<int> ransac_chunks(int max_iterations, bool lone = false) {
     return v;
 }
 
+// The RANSAC scratch of a frame of cap ≥ 1 rows, laid out from p on, every piece on a 256-B boundary;
+// p ends behind the last piece, so the one sequence both carves the scratch and sizes it.
+RansacFrame ransac_carve(char*& p, int cap, int* rng) {
+    const size_t c = (size_t)cap;
+    const int nb = solve_blocks(cap);
+    RansacFrame F{};
+    F.cap = cap;
+    F.all = carve<double>(p, 10 * c + 8);
+    F.inl = carve<double>(p, 10 * c + 8);
+    F.blkcnt = carve<int>(p, nb + 1);
+    F.blkw = carve<double>(p, nb + 1);
+    F.cnt_all = carve<int>(p, 1);
+    F.cnt_in = carve<int>(p, 1);
+    F.wsum = carve<double>(p, 1);
+    F.R.rng = rng;
+    F.R.counts = carve<int>(p, kHypMax);
+    F.R.T = carve<double>(p, (size_t)kHypMax * 16);
+    F.R.best = carve<int>(p, 1);
+    F.R.evaluated = carve<int>(p, 1);
+    F.R.rdone = carve<int>(p, 1);
+    F.R.bestT = carve<double>(p, 16);
+    F.R.active = carve<int>(p, 1);
+    F.Dv = drpm_carve(p, nb);
+    return F;
+}
+
 }  // namespace
 
 size_t ransac_bytes(int cap) {
-    // the carve sequence of launch_solve, each piece rounded up to 256 B (+ slack per piece)
-    const size_t c = (size_t)std::max(cap, 1);
-    const size_t nb = (c + kBlock - 1) / kBlock + 1;
-    return 2 * (10 * c + 8) * 8 + nb * (4 + 8) + (size_t)kHypMax * (4 + 16 * 8) + nb * kDrpmSlab * 8 +
-           (36 + 6 + 36 + 6 + 16) * 8 + 32 * 256;
+    char* p = nullptr;                 // a null base: the end of the carve is its size
+    ransac_carve(p, std::max(cap, 1), nullptr);
+    return (size_t)reinterpret_cast<uintptr_t>(p);
 }
 
-void launch_solve(hipStream_t s, const SolveLaunch& L) {
+RansacFrame ransac_frame(void* scratch, int cap, int* rng) {
+    char* p = (char*)scratch;
+    return ransac_carve(p, std::max(cap, 1), rng);
+}
+
+void launch_ransac(hipStream_t s, const SolveLaunch& L) {
     const KParams& kp = L.kp;
+    const RansacParams& rp = L.ransac;
     SolveState st = L.st;
-    if (kp.solve_method == IMLS_SOLVE_DRPM) {
-        // stand-alone SolveMotionEstimationProblemDRPM (solver.cpp:499-603) on host fp64 rows + weights
-        const int cap = std::max(L.N, 1);
-        const int b1 = solve_blocks(cap);
-        char* p = (char*)L.scratch;
-        auto carve = [&](size_t bytes) { char* r = p; p += (bytes + 255) / 256 * 256; return r; };
-        int* cnt = (int*)carve(64);
-        DrpmDev Dv;
-        Dv.H = (double*)carve(36 * 8);
-        Dv.g = (double*)carve(6 * 8);
-        Dv.U = (double*)carve(36 * 8);
-        Dv.ev = (double*)carve(6 * 8);
-        Dv.slabs = (double*)carve((size_t)(b1 + 1) * kDrpmSlab * 8);
-        const size_t c = (size_t)L.N;
-        k_set_count<<<1, 64, 0, s>>>(cnt, L.N);
-        k_drpm_guard<<<1, 64, 0, s>>>(cnt, L.st);
-        Rows rows{nullptr, nullptr, nullptr, L.rows_d, L.rows_d + 3 * c, L.rows_d + 6 * c, L.weights, 1, cnt, nullptr};
-        launch_rows_pass1(s, rows, cap, L.st.partial1, b1);
-        k_drpm_eig<<<1, 256, 0, s>>>(L.st.partial1, b1, L.st, Dv);
-        k_drpm_noise<<<b1, kBlock, 0, s>>>(rows, cap, L.st, Dv, L.ransac.drpm_stdev_points, L.ransac.drpm_stdev_normals);
-        k_drpm_final<<<1, 256, 0, s>>>(b1, L.st, Dv, L.tr, kp, L.ransac.drpm_threshold, cnt, cnt, L.update_pose,
-                                       RansacDev{}, nullptr);
-        return;
-    }
-    if (kp.solve_method != IMLS_SOLVE_RANSAC) {
-        launch_solve_chain(s, L.N, L.blocks1, kp, L.cs, L.cd, L.cn, L.rows_d, L.weights, st, L.tr, L.update_pose,
-                           L.rows_are_double, L.count);
-        return;
-    }
     const int cap = std::max(L.N, 1);
     const size_t c = (size_t)cap;
-    const int nb = (cap + kBlock - 1) / kBlock;
     const RansacFrame F = ransac_frame(L.scratch, cap, L.rng);
     const RansacDev& R = F.R;
     const int* done = L.st.done;
-
-    // one compaction (valid rows → all, or inliers → inl) with its post step folded in
-    auto compact = [&](const Source& src, int n, const CompactOut& out, int kind) {
-        const CompactPost P{kind, kp.correspond_number, L.update_pose, L.st, L.tr, R};
-        if (cap <= kCompactOne) {
-            k_compact_one<<<1, 1024, 0, s>>>(src, n, out, P);
-        } else {
-            k_compact_count<<<nb, kBlock, 0, s>>>(src, n, F.blkcnt, F.blkw, done);
-            k_compact_scan<<<1, 1024, 0, s>>>(F.blkcnt, F.blkw, nb, out, P);
-            k_compact_scatter<<<nb, kBlock, 0, s>>>(src, n, F.blkcnt, out, done);
-        }
-    };
+    // what follows a compaction (kind 1: the count gate and the selection reset; 2: the empty-set check)
+    auto post = [&](int kind) { return CompactPost{kind, kp.correspond_number, L.update_pose, L.st, L.tr, R}; };
 
     // 1. compact the valid correspondences (fp64 rows from the host API are already compact), then
     //    the count gate and the selection reset
     if (!L.rows_are_double) {
-        Source src{};
-        src.cs = L.cs; src.cd = L.cd; src.cn = L.cn;
-        compact(src, L.N, CompactOut{F.all, F.cnt_all, nullptr, cap}, 1);
+        launch_compact(s, Source::valid(L.cs, L.cd, L.cn), L.N, CompactOut::valid(F), post(1), F);
     } else {
         (void)hipMemcpyAsync(F.all, L.rows_d, 9 * c * 8, hipMemcpyDeviceToDevice, s);
-        k_set_count<<<1, 64, 0, s>>>(F.cnt_all, L.N);
+        launch_set_count(s, F.cnt_all, L.N);
         k_ransac_begin<<<1, 64, 0, s>>>(F.cnt_all, kp.correspond_number, L.update_pose, L.st, L.tr, R);
     }
     // 2. hypotheses in chunks, 256 threads per hypothesis (a lone frame's chunk has ~1 block per CU, so
@@ -1373,58 +733,44 @@ void launch_solve(hipStream_t s, const SolveLaunch& L) {
     // head of k_drpm_head_small (one launch fewer per ICP iteration).
     // Two chunks whose draws fit the jump table (the shipped 5000 hypotheses: 272 + 4728) run without a
     // selection between them (k_ransac_hyp, base > 0): one selection over both, at the head.
-    const std::vector<int> chunks = ransac_chunks(L.ransac.max_iterations, true);
-    const bool fold_select = L.ransac.final_method == IMLS_FINAL_DRPM && cap <= kSmallRows;
+    const std::vector<int> chunks = ransac_chunks(rp.max_iterations, true);
+    const bool fold_select = rp.final_method == IMLS_FINAL_DRPM && cap <= kSmallRows;
     const bool one_select = fold_select && chunks.size() == 2 && chunks[0] + chunks[1] <= kHypMax;
     int sel_chunk = chunks.back();
     if (one_select) {
-        k_ransac_hyp<256><<<chunks[0], 256, 0, s>>>(F.all, F.cnt_all, cap, R, L.ransac.distance_threshold, chunks[0],
-                                                    done, 0, 0.0);
-        k_ransac_hyp<256><<<chunks[1], 256, 0, s>>>(F.all, F.cnt_all, cap, R, L.ransac.distance_threshold, chunks[1],
-                                                    done, chunks[0], L.ransac.min_inliers_percentage);
+        k_ransac_hyp<256><<<chunks[0], 256, 0, s>>>(F.all, F.cnt_all, cap, R, rp.distance_threshold, chunks[0], done, 0, 0.0);
+        k_ransac_hyp<256><<<chunks[1], 256, 0, s>>>(F.all, F.cnt_all, cap, R, rp.distance_threshold, chunks[1], done,
+                                                    chunks[0], rp.min_inliers_percentage);
         sel_chunk = chunks[0] + chunks[1];
     } else {
         for (size_t ci = 0; ci < chunks.size(); ++ci) {
             const int cn = chunks[ci];
-            k_ransac_hyp<256><<<cn, 256, 0, s>>>(F.all, F.cnt_all, cap, R, L.ransac.distance_threshold, cn, done, 0, 0.0);
+            k_ransac_hyp<256><<<cn, 256, 0, s>>>(F.all, F.cnt_all, cap, R, rp.distance_threshold, cn, done, 0, 0.0);
             if (!(fold_select && ci + 1 == chunks.size()))
-                k_ransac_select<<<1, 64, 0, s>>>(F.cnt_all, R, cn, L.ransac.max_iterations, L.ransac.min_inliers_percentage,
-                                                 done);
+                k_ransac_select<<<1, 64, 0, s>>>(F.cnt_all, R, cn, rp.max_iterations, rp.min_inliers_percentage, done);
         }
     }
 
-    // 3. inliers of the best Δ with their Huber-like weights (order kept), Σw; an empty set stops
-    Source isrc{};
-    isrc.rows = F.all;
-    isrc.count = F.cnt_all;
-    isrc.cap = cap;
-    isrc.T = R.bestT;
-    isrc.dist_thr = L.ransac.distance_threshold;
-    isrc.h2 = L.ransac.huber_threshold * L.ransac.distance_threshold;
-    KParams fk = kp;
-    fk.correspond_number = 0;                       // the count gate ran before RANSAC
+    // 3. inliers of the best Δ with their Huber-like weights (order kept), Σw; an empty set stops.  A
+    // small DRPM frame: the compaction, pass 1 and the eigendecomposition in one launch (the chain's values)
+    const Source isrc = Source::inliers(F, rp.distance_threshold, rp.huber_threshold * rp.distance_threshold);
     double* inl = F.inl;
-    Rows rows{nullptr, nullptr, nullptr, inl, inl + 3 * c, inl + 6 * c, inl + 9 * c, 1, F.cnt_in, F.wsum};
-    if (L.ransac.final_method == IMLS_FINAL_DRPM && cap <= kSmallRows) {
-        // a small frame: compaction + pass 1 + eigendecomposition in one launch (the chain's values),
-        // then the noise terms and the solve
-        const int b1 = solve_blocks(cap);
-        const CompactPost P{2, kp.correspond_number, L.update_pose, L.st, L.tr, R};
-        const SelectArgs sel{F.cnt_all, sel_chunk, L.ransac.max_iterations, L.ransac.min_inliers_percentage};
-        k_drpm_head_small<<<1, kHeadThreads, 0, s>>>(sel, isrc, cap, CompactOut{F.inl, F.cnt_in, F.wsum, cap}, P, rows, b1,
+    const Rows rows{nullptr, nullptr, nullptr, inl, inl + 3 * c, inl + 6 * c, inl + 9 * c, 1, F.cnt_in, F.wsum};
+    if (fold_select) {
+        const SelectArgs sel{F.cnt_all, sel_chunk, rp.max_iterations, rp.min_inliers_percentage};
+        k_drpm_head_small<<<1, kHeadThreads, 0, s>>>(sel, isrc, cap, CompactOut::inliers(F), post(2), rows, solve_blocks(cap),
                                                      L.st, F.Dv);
-        k_drpm_noise<<<b1, kBlock, 0, s>>>(rows, cap, L.st, F.Dv, L.ransac.drpm_stdev_points, L.ransac.drpm_stdev_normals);
-        k_drpm_final<<<1, 256, 0, s>>>(b1, L.st, F.Dv, L.tr, fk, L.ransac.drpm_threshold, F.cnt_all, F.cnt_in, L.update_pose,
-                                       R, L.tr);
-        return;
+    } else {
+        launch_compact(s, isrc, cap, CompactOut::inliers(F), post(2), F);
     }
-    compact(isrc, cap, CompactOut{F.inl, F.cnt_in, F.wsum, cap}, 2);
 
     // 4. final solve on the inliers (+ RANSAC's own trace record)
-    switch (L.ransac.final_method) {
+    KParams fk = kp;
+    fk.correspond_number = 0;                       // the count gate ran before RANSAC
+    switch (rp.final_method) {
         case IMLS_FINAL_LS:
             fk.solve_method = IMLS_SOLVE_LS;
-            fk.ls_threshold = L.ransac.ls_threshold;
+            fk.ls_threshold = rp.ls_threshold;
             launch_solve_chain(s, cap, 0, fk, nullptr, nullptr, nullptr, inl, nullptr, st, L.tr, L.update_pose, 1, F.cnt_in, nullptr);
             if (L.tr) k_ransac_trace<<<1, 64, 0, s>>>(F.cnt_all, R, L.tr);
             break;
@@ -1433,73 +779,24 @@ void launch_solve(hipStream_t s, const SolveLaunch& L) {
             launch_solve_chain(s, cap, 0, fk, nullptr, nullptr, nullptr, inl, inl + 9 * c, st, L.tr, L.update_pose, 1, F.cnt_in, F.wsum);
             if (L.tr) k_ransac_trace<<<1, 64, 0, s>>>(F.cnt_all, R, L.tr);
             break;
-        default: {   // DRPM
-            const int b1 = solve_blocks(cap);
-            launch_rows_pass1(s, rows, cap, L.st.partial1, b1);
-            k_drpm_eig<<<1, 256, 0, s>>>(L.st.partial1, b1, L.st, F.Dv);
-            k_drpm_noise<<<b1, kBlock, 0, s>>>(rows, cap, L.st, F.Dv, L.ransac.drpm_stdev_points, L.ransac.drpm_stdev_normals);
-            k_drpm_final<<<1, 256, 0, s>>>(b1, L.st, F.Dv, L.tr, fk, L.ransac.drpm_threshold, F.cnt_all, F.cnt_in, L.update_pose,
-                                           R, L.tr);
-        }
+        default:   // DRPM (the head has run pass 1 and the eigendecomposition of a small frame)
+            launch_drpm(s, rows, cap, L.st, F.Dv, L.tr, fk, rp, F.cnt_all, F.cnt_in, L.update_pose, R, L.tr, fold_select);
     }
-}
-
-RansacFrame ransac_frame(void* scratch, int cap, int* rng) {
-    // the carve sequence sized by ransac_bytes, each piece rounded up to 256 B
-    const size_t c = (size_t)std::max(cap, 1);
-    const int nb = (int)((c + kBlock - 1) / kBlock);
-    char* p = (char*)scratch;
-    auto carve = [&](size_t bytes) { char* r = p; p += (bytes + 255) / 256 * 256; return r; };
-    RansacFrame F{};
-    F.cap = (int)c;
-    F.all = (double*)carve((10 * c + 8) * 8);
-    F.inl = (double*)carve((10 * c + 8) * 8);
-    F.blkcnt = (int*)carve((size_t)(nb + 1) * 4);
-    F.blkw = (double*)carve((size_t)(nb + 1) * 8);
-    F.cnt_all = (int*)carve(64);
-    F.cnt_in = (int*)carve(64);
-    F.wsum = (double*)carve(64);
-    F.R.rng = rng;
-    F.R.counts = (int*)carve((size_t)kHypMax * 4);
-    F.R.T = (double*)carve((size_t)kHypMax * 16 * 8);
-    F.R.best = (int*)carve(64);
-    F.R.evaluated = (int*)carve(64);
-    F.R.rdone = (int*)carve(64);
-    F.R.bestT = (double*)carve(16 * 8);
-    F.R.active = (int*)carve(64);
-    F.Dv.H = (double*)carve(36 * 8);
-    F.Dv.g = (double*)carve(6 * 8);
-    F.Dv.U = (double*)carve(36 * 8);
-    F.Dv.ev = (double*)carve(6 * 8);
-    F.Dv.slabs = (double*)carve((size_t)(nb + 1) * kDrpmSlab * 8);
-    return F;
 }
 
 int launch_ransac_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp,
                         const RansacParams& rp, int it) {
     if (npairs <= 0) return 0;
-    if (npairs > kMaxRansacBatch) return -1;   // the select kernels keep one slot per frame in LDS
+    if (npairs > kMaxRansacBatch) return -1;   // the hypothesis kernels keep one slot per frame in LDS
     std::vector<int> caps((size_t)npairs);
     int maxc = 1;
     for (int k = 0; k < npairs; ++k) {
         caps[k] = std::max(n_host[k], 1);
         maxc = std::max(maxc, caps[k]);
     }
-    const dim3 gc((maxc + kBlock - 1) / kBlock, npairs), g1(1, npairs);
-    const double h2 = rp.huber_threshold * rp.distance_threshold;
-    // one compaction per frame (mode 0: valid rows → all, then the count gate and selection reset;
-    // mode 1: the inliers of the best Δ, then the empty-set check)
-    auto compact = [&](int mode, double dt, double hh) {
-        if (maxc <= kCompactOne) {
-            k_compact_one_b<<<g1, 1024, 0, s>>>(tab, mode, dt, hh, kp.correspond_number, it);
-        } else {
-            k_compact_count_b<<<gc, kBlock, 0, s>>>(tab, mode, dt, hh);
-            k_compact_scan_b<<<g1, 1024, 0, s>>>(tab, mode, kp.correspond_number, it);
-            k_compact_scatter_b<<<gc, kBlock, 0, s>>>(tab, mode, dt, hh);
-        }
-    };
+    const dim3 g1(1, npairs);
     // 1. every frame's valid correspondences, compacted (order kept) to fp64
-    compact(0, 0.0, 0.0);
+    launch_compact_batch(s, tab, npairs, maxc, 0, 0.0, 0.0, kp.correspond_number, it);
     // 2. hypotheses: each chunk's items of the still-running frames spread over one grid
     for (const int cn : ransac_chunks(rp.max_iterations)) {
         const int grid = std::min(cn * npairs, kHypGrid);
@@ -1510,27 +807,23 @@ int launch_ransac_batch(hipStream_t s, const PairDev* tab, const int* n_host, in
         k_ransac_select_b<<<g1, 64, 0, s>>>(tab, cn, rp.max_iterations, rp.min_inliers_percentage);
     }
     // 3. inliers of each frame's best Δ with their weights
-    compact(1, rp.distance_threshold, h2);
-    // 4. final solve
+    launch_compact_batch(s, tab, npairs, maxc, 1, rp.distance_threshold, rp.huber_threshold * rp.distance_threshold,
+                         kp.correspond_number, it);
+    // 4. final solve (+ RANSAC's trace record: the DRPM final writes it itself)
     KParams fk = kp;
     fk.correspond_number = 0;
     switch (rp.final_method) {
         case IMLS_FINAL_LS:
-            fk.solve_method = IMLS_SOLVE_LS;
             fk.ls_threshold = rp.ls_threshold;
-            launch_solve_batch(s, tab, caps.data(), npairs, fk, it, 1);
-            break;
+            [[fallthrough]];
         case IMLS_FINAL_WEIGHTED_LS:
-            fk.solve_method = IMLS_SOLVE_WEIGHTED_LS;
+            fk.solve_method = rp.final_method == IMLS_FINAL_LS ? IMLS_SOLVE_LS : IMLS_SOLVE_WEIGHTED_LS;
             launch_solve_batch(s, tab, caps.data(), npairs, fk, it, 1);
+            k_ransac_trace_b<<<g1, 64, 0, s>>>(tab, it);
             break;
         default:
-            launch_rows_pass1_batch(s, tab, caps.data(), npairs, 1);
-            k_drpm_eig_b<<<g1, 256, 0, s>>>(tab);
-            k_drpm_noise_b<<<dim3(solve_blocks_of(maxc), npairs), kBlock, 0, s>>>(tab, rp.drpm_stdev_points, rp.drpm_stdev_normals);
-            k_drpm_final_b<<<g1, 256, 0, s>>>(tab, fk, rp.drpm_threshold, it);   // + RANSAC's trace record
+            launch_drpm_batch(s, tab, caps.data(), npairs, maxc, fk, rp, it);
     }
-    if (rp.final_method == IMLS_FINAL_LS || rp.final_method == IMLS_FINAL_WEIGHTED_LS) k_ransac_trace_b<<<g1, 64, 0, s>>>(tab, it);
     return 0;
 }
 

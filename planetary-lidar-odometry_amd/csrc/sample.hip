@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "solve.h"
 
 namespace imlsgpu {
 namespace {

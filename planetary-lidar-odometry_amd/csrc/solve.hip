@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "solve.h"
 #include "solve_common.h"
 
 namespace imlsgpu {
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(NT) void k_rows_pass1(Rows rows, int N, double* __r
 // batched: every frame's RANSAC inlier rows (grid y = frame)
 __global__ __launch_bounds__(kBlock) void k_rows_pass1_b(const PairDev* __restrict__ tab, int weighted) {
     const PairDev A = device_view(tab + blockIdx.y);
-    if ((int)blockIdx.x >= solve_blocks_of(A.rf.cap)) return;
+    if ((int)blockIdx.x >= solve_blocks(A.rf.cap)) return;
     rows_pass1_body<kBlock>(frame_rows(A, 1, weighted), A.rf.cap, A.st.partial1);
 }
 
@@ -796,7 +797,7 @@ __host__ __device__ __forceinline__ int pass1_blocks_of(int N) {   // project_bl
     return (N + kPass1Block - 1) / kPass1Block + kPass1Fallback;
 }
 // batched chain: src 0 = the projection's float rows (k_solve_small for N ≤ kSmallRows, the grid
-// chain above), src 1 = the RANSAC inlier rows (the grid chain always, as launch_solve runs it)
+// chain above), src 1 = the RANSAC inlier rows (the grid chain always, as launch_ransac runs it)
 __device__ __forceinline__ int frame_rows_n(const PairDev& A, int src) { return src ? A.rf.cap : A.N; }
 __device__ __forceinline__ bool frame_big(const PairDev& A, int src) { return src || A.N > kSmallRows; }
 
@@ -810,7 +811,7 @@ __global__ __launch_bounds__(256) void k_solve_first_b(const PairDev* __restrict
                                                        int src) {
     const PairDev A = device_view(tab + blockIdx.y);
     if (!frame_big(A, src)) return;
-    solve_first_body(A.st.partial1, src ? solve_blocks_of(A.rf.cap) : pass1_blocks_of(A.N), A.st, A.trace + it, kp,
+    solve_first_body(A.st.partial1, src ? solve_blocks(A.rf.cap) : pass1_blocks_of(A.N), A.st, A.trace + it, kp,
                      weighted, 1);
 }
 __global__ __launch_bounds__(kResidBlock) void k_resid_hist_b(const PairDev* __restrict__ tab, int src) {
@@ -835,8 +836,6 @@ __global__ __launch_bounds__(kFinalBlock) void k_solve_final_b(const PairDev* __
 }
 
 }  // namespace
-
-int solve_blocks(int N) { return (N + kBlock - 1) / kBlock; }
 
 void launch_rows_pass1(hipStream_t s, const Rows& rows, int N, double* partial, int blocks) {
     k_rows_pass1<kBlock><<<blocks, kBlock, 0, s>>>(rows, N, partial);
@@ -883,7 +882,7 @@ namespace imlsgpu {
 void launch_rows_pass1_batch(hipStream_t s, const PairDev* tab, const int* cap_host, int npairs, int weighted) {
     int maxc = 1;
     for (int k = 0; k < npairs; ++k) maxc = std::max(maxc, cap_host[k]);
-    k_rows_pass1_b<<<dim3(solve_blocks_of(maxc), npairs), kBlock, 0, s>>>(tab, weighted);
+    k_rows_pass1_b<<<dim3(solve_blocks(maxc), npairs), kBlock, 0, s>>>(tab, weighted);
 }
 
 void launch_solve_batch(hipStream_t s, const PairDev* tab, const int* n_host, int npairs, const KParams& kp, int it,

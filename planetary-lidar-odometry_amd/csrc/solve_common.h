@@ -1,5 +1,5 @@
-// solve_common.h — device helpers shared by the LS chain (solve.hip) and the RANSAC / DRPM
-// solvers (ransac.hip): the correspondence-row accessor, block reductions, the 6×6 column-pivoted
+// solve_common.h — device helpers shared by the LS chain (solve.hip), the robust solve and the
+// RANSAC / DRPM solvers (ransac.hip, compact_rows.hip, drpm.hip): the correspondence-row accessor, block reductions, the 6×6 column-pivoted
 // solve, Δ from x (Rodrigues + polar factor) and the pose update / convergence test.
 #pragma once
 #include <cfloat>
@@ -58,7 +58,7 @@ __device__ __forceinline__ double robust_psi(int loss, double c, double r) {
 }
 
 // Rows of a batched frame: the projection's float rows (src 0) or the frame's RANSAC inlier rows
-// (src 1: fp64, device-side count; weights w / Σw when weighted) — what launch_solve builds for the
+// (src 1: fp64, device-side count; weights w / Σw when weighted) — what launch_ransac builds for the
 // same solve of a one-frame launch.
 __device__ __forceinline__ Rows frame_rows(const PairDev& A, int src, int weighted) {
     if (!src) return Rows{A.cs, A.cd, A.cn, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
@@ -67,7 +67,6 @@ __device__ __forceinline__ Rows frame_rows(const PairDev& A, int src, int weight
     return Rows{nullptr, nullptr, nullptr, r, r + 3 * c, r + 6 * c, weighted ? r + 9 * c : nullptr, 1, A.rf.cnt_in,
                 weighted ? A.rf.wsum : nullptr};
 }
-__host__ __device__ __forceinline__ int solve_blocks_of(int N) { return (N + kBlock - 1) / kBlock; }
 
 // pass 1 of the LS chain (weighted normal equations) on any rows; solve.hip
 void launch_rows_pass1(hipStream_t s, const Rows& rows, int N, double* partial, int blocks);
@@ -80,12 +79,9 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// Block-reduce the 28 normal-equation terms of (a, b, weight, count); result valid in thread 0's
-// `out` (all threads must call).  red: [nwaves][28] LDS.
-template <int NT>
-__device__ void block_normeq(const double a[6], double b, double cnt, double* red, double out[kNormEq]) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double v[32];
+// A row's 28 normal-equation terms — a aᵀ upper triangle (21), a·b (6), the count — as wave_sum28
+// takes them (v[28..31] = 0).
+__device__ __forceinline__ void normeq_terms(const double a[6], double b, double cnt, double (&v)[32]) {
     int k = 0;
 #pragma unroll
     for (int r = 0; r < 6; ++r)
@@ -96,6 +92,15 @@ __device__ void block_normeq(const double a[6], double b, double cnt, double* re
     v[27] = cnt;
 #pragma unroll
     for (int q = kNormEq; q < 32; ++q) v[q] = 0.0;
+}
+
+// Block-reduce the 28 normal-equation terms of (a, b, weight, count); result valid in thread 0's
+// `out` (all threads must call).  red: [nwaves][28] LDS.
+template <int NT>
+__device__ void block_normeq(const double a[6], double b, double cnt, double* red, double out[kNormEq]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double v[32];
+    normeq_terms(a, b, cnt, v);
     const double s = wave_sum28(v);
     if (!(lane & 1) && (lane >> 1) < kNormEq) red[wv * kNormEq + (lane >> 1)] = s;
     __syncthreads();

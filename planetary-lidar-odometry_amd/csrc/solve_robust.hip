@@ -16,6 +16,7 @@
 //                                the last one does Δ and the pose update).  2K launches.
 // Grid shapes and the order of every sum depend on N only.  Every kernel returns at once when the
 // frame's `done` flag is set; ordinary vector stores, no floating-point atomics.
+#include "solve.h"
 #include "solve_common.h"
 
 namespace imlsgpu {
@@ -266,13 +267,13 @@ __global__ __launch_bounds__(kSmallBlock) void k_robust_small_b(const PairDev* _
 }
 __global__ __launch_bounds__(kBlock) void k_robust_pass_b(const PairDev* __restrict__ tab, KParams kp, int it) {
     const PairDev A = device_view(tab + blockIdx.y);
-    if (A.N <= kSmallRows || (int)blockIdx.x >= solve_blocks_of(A.N)) return;
+    if (A.N <= kSmallRows || (int)blockIdx.x >= solve_blocks(A.N)) return;
     robust_pass_body(frame_rows(A, 0, 0), A.N, A.st, kp, it);
 }
 __global__ __launch_bounds__(kStepBlock) void k_robust_step_b(const PairDev* __restrict__ tab, KParams kp, int it, int iter) {
     const PairDev A = device_view(tab + blockIdx.y);
     if (A.N <= kSmallRows) return;
-    robust_step_body(solve_blocks_of(A.N), A.st, A.trace + iter, kp, it, 1);
+    robust_step_body(solve_blocks(A.N), A.st, A.trace + iter, kp, it, 1);
 }
 
 }  // namespace
@@ -289,7 +290,7 @@ void launch_solve_robust(hipStream_t s, const SolveLaunch& L) {
         k_robust_small<<<1, kSmallBlock, 0, s>>>(rows, N, L.st, L.tr, L.kp, L.update_pose);
         return;
     }
-    const int nb = std::max(solve_blocks_of(N), 1);
+    const int nb = std::max(solve_blocks(N), 1);
     for (int it = 0; it < L.kp.robust_iters; ++it) {
         k_robust_pass<<<nb, kBlock, 0, s>>>(rows, N, L.st, L.kp, it);
         k_robust_step<<<1, kStepBlock, 0, s>>>(nb, L.st, L.tr, L.kp, it, L.update_pose);
@@ -307,7 +308,7 @@ void launch_solve_robust_batch(hipStream_t s, const PairDev* tab, const int* n_h
     if (any_small) k_robust_small_b<<<dim3(1, npairs), kSmallBlock, 0, s>>>(tab, kp, it);
     if (!any_large) return;
     for (int k = 0; k < kp.robust_iters; ++k) {
-        k_robust_pass_b<<<dim3(solve_blocks_of(maxN), npairs), kBlock, 0, s>>>(tab, kp, k);
+        k_robust_pass_b<<<dim3(solve_blocks(maxN), npairs), kBlock, 0, s>>>(tab, kp, k);
         k_robust_step_b<<<dim3(1, npairs), kStepBlock, 0, s>>>(tab, kp, k, it);
     }
 }

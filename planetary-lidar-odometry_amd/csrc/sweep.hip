@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "solve.h"
 
 namespace imlsgpu {
 namespace {

@@ -2,7 +2,7 @@
 which proves on the CPU oracle alone that each case does what it is meant to, and
 test_gpu_ransac_sizes.py, which runs them on the device).  No GPU imports.
 
-csrc/ransac.hip changes its code path at three row counts: > 4096 rows (kSmallRows: grid inlier
+The RANSAC solve (csrc/ransac.hip, compact_rows.hip, drpm.hip) changes its code path at three row counts: > 4096 rows (kSmallRows: grid inlier
 compaction, grid pass 1 and LS chain instead of the one-launch head; 256-thread hypothesis blocks in
 the batched launch), > 16384 rows (kCompactOne: three-kernel compaction instead of one block) and,
 for a lone frame, at hypothesis 272 and 8464 (the chunk edges 272 + 8192 + …).

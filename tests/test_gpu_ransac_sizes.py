@@ -1,5 +1,6 @@
-"""GPU parity of the RANSAC solve path with the oracle ABOVE the sizes where csrc/ransac.hip changes
-its code path (tests/test_gpu_ransac.py stays at ≤ 4000 rows):
+"""GPU parity of the RANSAC solve path with the oracle ABOVE the sizes where the RANSAC solve
+(csrc/ransac.hip, compact_rows.hip, drpm.hip) changes its code path (tests/test_gpu_ransac.py stays
+at ≤ 4000 rows):
 
   > 4096 rows   grid inlier compaction, grid pass 1 + k_drpm_eig and the grid LS chain instead of
                 k_drpm_head_small / the folded selection; 256-thread hypothesis blocks when batched
